@@ -10,14 +10,22 @@ random-init weights of the same architecture, trainable_backbone_layers=3 as in 
 Arithmetic: the headline runs the reference's precision -- an fp32 model (train_frcnn_baseline.py:139-176,
 no autocast; TF32 convs on its Ampere GPU): HipBackend("f32"), f32 activations / gradients / BN /
 RoIAlign, every conv product as the bf16x3 split on MFMA (~2^-16 relative, finer than TF32's 2^-11;
-tests/test_gpu_x3.py). The bf16 mode (bf16 activations and operands) is timed after it and reported
-inside the same line under "bf16_variant" (--precision f32|bf16 picks one mode only). The same line
-also carries "augment_variant" (configs[2]'s step with on-GPU RandomCorruption), and the metric's
-"+ eval" half: "eval_variant" (eval_all.py per-image eval forward) and "eval_restored_variant"
-(configs[3]: U-Net restore + eval), K images each after W warmup (--no-eval-variant skips them;
-mAP@50 is parity-unpinned: no trained checkpoint ships with the reference).
+tests/test_gpu_x3.py). A plain run does only that: set up, W warmup steps, K timed steps, one JSON line
+(--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy, see dump_outputs).
+The conv tuner's choices are pinned from bench_tune.json (load_tune_table), so that every run launches
+the same kernels and two runs with the same arguments compute bit-identical outputs.
 
-    python bench.py [--gpus N --steps K --warmup W]
+With --full the other legs follow the headline. The bf16 mode (bf16 activations and operands) is timed
+after it and reported inside the same line under "bf16_variant" (--precision f32|bf16 picks one mode
+only). The same line also carries "roofline" / "hbm_ops" (per-kernel timing of an eager step),
+"augment_variant" (configs[2]'s step with on-GPU RandomCorruption), the metric's "+ eval" half:
+"eval_variant" (eval_all.py per-image eval forward) and "eval_restored_variant" (configs[3]: U-Net
+restore + eval), K images each after W warmup (--no-eval-variant skips them; mAP@50 is
+parity-unpinned: no trained checkpoint ships with the reference), and "cpu_baseline" (the oracle CPU
+port of the step). The other --mode runs likewise run their conv_roofline / CPU baseline legs under
+--full only.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -66,7 +74,9 @@ def make_optimizer(model):
     return SGD(params, lr=0.005, momentum=0.9, weight_decay=0.0005)
 
 
-def train_step(model, opt, images, targets, augment=False, gen=None, as_list=False):
+def train_step(model, opt, images, targets, augment=False, gen=None, as_list=False, out=None):
+    """One timed step; returns the summed loss. `out` (a dict), when given, receives the step's loss
+    tensors by name (--dump-outputs passes it for the last timed step only)."""
     if augment:
         from mx_det import ops
         B = images.shape[0]
@@ -82,7 +92,76 @@ def train_step(model, opt, images, targets, augment=False, gen=None, as_list=Fal
     if hasattr(model, "sync_gradients"):  # mx_det.dp.DataParallel
         model.sync_gradients()
     opt.step()
+    if out is not None:
+        out.update({k: v.detach() for k, v in loss_dict.items()}, loss_total=losses.detach())
     return float(losses.item())
+
+
+TUNE_FILE = os.path.join(ROOT, "bench_tune.json")
+
+
+def _tune_key(k, enc):
+    """A conv tuner key (nested tuples of ints / bools / torch dtypes) to JSON lists and back."""
+    if isinstance(k, (list, tuple)):
+        return (list if enc else tuple)(_tune_key(e, enc) for e in k)
+    if enc:
+        return str(k) if isinstance(k, torch.dtype) else k
+    return getattr(torch, k[len("torch."):]) if isinstance(k, str) and k.startswith("torch.") else k
+
+
+def load_tune_table(path=TUNE_FILE):
+    """Pin the conv tuner's choices for the benchmark's shapes (bench_tune.json: launch settings the
+    tuner picked on an MI355X, the most frequent pick of several runs) by seeding mx_det.conv's
+    in-process cache. Left to itself the tuner times its candidates at first use, and timing noise lets
+    near-equal candidates (other split-K factors, i.e. another summation order) win in different runs;
+    the rounding-level differences grow over the training steps, so two runs of one build would not
+    compute the same numbers. A shape the table lacks is tuned live as before; MX_BENCH_TUNE_TABLE=0
+    ignores the table. Returns the number of entries pinned."""
+    if os.environ.get("MX_BENCH_TUNE_TABLE", "1") == "0" or not os.path.exists(path):
+        return 0
+    from mx_det import conv as mc
+    with open(path) as f:
+        entries = json.load(f)["entries"]
+    for k, cfg in entries:
+        mc._tune_cache.setdefault(_tune_key(k, False), tuple(cfg))
+    return len(entries)
+
+
+def save_tune_table(path):
+    """--save-tune: the conv tuner's cache after the run (what load_tune_table reads back)."""
+    from mx_det import conv as mc
+    entries = sorted(([_tune_key(k, True), list(c)] for k, c in mc._tune_cache.items()), key=json.dumps)
+    with open(path, "w") as f:
+        json.dump({"device": torch.cuda.get_device_properties(0).gcnArchName.split(":")[0], "entries": entries}, f, indent=0)
+
+
+DUMP_SAMPLE = 4096  # elements kept per parameter tensor by --dump-outputs (all of a smaller one)
+
+
+def dump_outputs(path, last, model):
+    """--dump-outputs: what the last timed train step handed back, as float32 <name>.npy files under
+    `path`: each loss of the model's loss dict and their sum (what a caller of the step receives), and
+    the state the step left behind -- the trainable parameters after the optimizer update and their
+    gradients, each tensor as a fixed seeded sample of at most DUMP_SAMPLE elements (all parameters
+    would be ~170 MB), concatenated in named_parameters() order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in last.items():
+        np.save(os.path.join(path, k + ".npy"), v.float().cpu().numpy().astype(np.float32))
+    rng = np.random.default_rng(20240607)
+    params, grads = [], []
+    for _, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        n = p.numel()
+        idx = torch.from_numpy(np.sort(rng.choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE
+                               else np.arange(n)).to(p.device)
+        params.append(p.detach().reshape(-1)[idx].float().cpu())
+        if p.grad is not None:
+            grads.append(p.grad.detach().reshape(-1)[idx].float().cpu())
+    np.save(os.path.join(path, "params_sample.npy"), torch.cat(params).numpy().astype(np.float32))
+    if grads:
+        np.save(os.path.join(path, "grads_sample.npy"), torch.cat(grads).numpy().astype(np.float32))
 
 
 def host_threads():
@@ -409,9 +488,10 @@ def hbm_ops_roofline(model, opt, imgs, tg, reps=10):
     return res
 
 
-def _time_precision(precision, args, world, rank, dev, imgs, tg):
+def _time_precision(precision, args, world, rank, dev, imgs, tg, last=None):
     """Build the model in one arithmetic mode, run W warmup steps, time exactly K steps between
-    barrier + synchronize pairs; returns (model, ddp, opt, seconds over K steps, max over ranks)."""
+    barrier + synchronize pairs; returns (model, ddp, opt, seconds over K steps, max over ranks).
+    `last` (a dict) receives the loss tensors of the last timed step."""
     torch.manual_seed(42)
     model = build_model(dev, precision=precision).train()
     ddp = model
@@ -425,9 +505,9 @@ def _time_precision(precision, args, world, rank, dev, imgs, tg):
 
     as_list = os.environ.get("MX_BENCH_LIST") == "1"  # diagnostics: images as a list, as a DataLoader gives them
 
-    def step(i):
+    def step(i, out=None):
         j = (2 * i) % N_IMAGES_PER_RANK
-        return train_step(ddp, opt, imgs[j:j + 2], tg[j:j + 2], args.augment, gen, as_list)
+        return train_step(ddp, opt, imgs[j:j + 2], tg[j:j + 2], args.augment, gen, as_list, out)
 
     for i in range(args.warmup):
         step(i)
@@ -438,7 +518,7 @@ def _time_precision(precision, args, world, rank, dev, imgs, tg):
     _lib.trace_marker(1)  # timed-region markers for the rocprofv3 kernel trace (tools/prof_steps.py)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        step(args.warmup + i, last if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -826,7 +906,23 @@ def main():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-augment-variant", action="store_true")
     ap.add_argument("--no-eval-variant", action="store_true", help="skip the eval / eval_restored legs of the train run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg (roofline + hbm_ops, the bf16 / augment / "
+                         "eval variants, the CPU baseline; the --no-* switches drop single legs). Without it "
+                         "only the headline is set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="--mode train: after the timed steps write what the last one computed (its losses, a "
+                         "seeded sample of the updated parameters and their gradients) as float32 DIR/<name>.npy")
+    ap.add_argument("--save-tune", metavar="FILE",
+                    help="--mode train: write the conv tuner's choices after the headline steps to FILE "
+                         "(bench_tune.json's format; run with MX_BENCH_TUNE_TABLE=0 to tune every shape live)")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "train":
+        ap.error("--dump-outputs is implemented for --mode train")
+    if not args.full:  # the headline alone, in its own precision (f32 unless --precision bf16)
+        args.no_cpu_baseline = args.no_roofline = args.no_augment_variant = args.no_eval_variant = True
+        if args.precision == "both":
+            args.precision = "f32"
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `bench.py --gpus N` run directly: one rank per GPU needs a launcher. Start torch.distributed.run
@@ -861,6 +957,7 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
 
+    pinned = load_tune_table()
     from mx_det.data import synth_batch
     imgs, tg = synth_batch(rank * N_IMAGES_PER_RANK, N_IMAGES_PER_RANK, device=dev)
     if args.mode != "train":
@@ -880,7 +977,12 @@ def main():
         return
     precs = ["f32", "bf16"] if args.precision == "both" else [args.precision]
     head = precs[0]
-    model, ddp, opt, dt = _time_precision(head, args, world, rank, dev, imgs, tg)
+    last = {} if args.dump_outputs and rank == 0 else None
+    model, ddp, opt, dt = _time_precision(head, args, world, rank, dev, imgs, tg, last)
+    if last is not None:
+        dump_outputs(args.dump_outputs, last, model)
+    if args.save_tune and rank == 0:
+        save_tune_table(args.save_tune)
     images = 2 * args.steps * world
     rec = {
         "metric": "images/sec FRCNN-R50-FPN train @1333x800 bs=2/GPU",
@@ -900,7 +1002,8 @@ def main():
                                                                                    if args.augment else ""),
                    "global_batch": 2 * world, "per_gpu_batch": 2, "image": "1333x800 (padded 1344x800)",
                    "parallelism": f"dp{world}" + (" (nccl group, DataParallel)" if world == 1 and dist.is_initialized()
-                                                   else ""), "trainable_backbone_layers": 3},
+                                                   else ""), "trainable_backbone_layers": 3,
+                   "conv_tuner": f"bench_tune.json ({pinned} shapes pinned)" if pinned else "live"},
     }
     peak = {"f32": X3_PEAK_TFLOPS, "bf16": BF16_PEAK_TFLOPS}
     # the measurement legs run a train step through the data-parallel wrapper, whose gradient

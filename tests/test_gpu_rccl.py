@@ -59,7 +59,7 @@ def test_bench_line_under_nccl_group():
     env = _env()
     env["MX_BENCH_DP"] = "1"
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "2", "--precision", "f32",
-                        "--no-eval-variant", "--no-augment-variant", "--no-cpu-baseline"],
+                        "--full", "--no-eval-variant", "--no-augment-variant", "--no-cpu-baseline"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     rec = json.loads(p.stdout.strip().splitlines()[-1])

@@ -18,7 +18,7 @@ for s in $STEPS; do
         || { echo "smoke failed rc=$?"; tail -30 "$OUT/smoke.log"; exit 1; }
       tail -2 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 400 python -u bench.py > "$OUT/bench.log" 2>&1 \
+      timeout -k 10 400 python -u bench.py --full > "$OUT/bench.log" 2>&1 \
         || { echo "bench failed rc=$?"; tail -30 "$OUT/bench.log"; exit 1; }
       tail -1 "$OUT/bench.log" ;;
     script)
@@ -30,12 +30,12 @@ for s in $STEPS; do
         || { echo "breakdown failed rc=$?"; tail -30 "$OUT/breakdown.log"; exit 1; }
       tail -5 "$OUT/breakdown.log" ;;
     benchfast)
-      timeout -k 10 300 python -u bench.py --no-cpu-baseline > "$OUT/bench.log" 2>&1 \
+      timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > "$OUT/bench.log" 2>&1 \
         || { echo "bench failed rc=$?"; tail -30 "$OUT/bench.log"; exit 1; }
       tail -1 "$OUT/bench.log" ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o prof -- \
-        python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/prof.log" 2>&1 \
+        python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/prof.log" 2>&1 \
         || { echo "prof failed rc=$?"; tail -30 "$OUT/prof.log"; exit 1; }
       for f in $(find "$OUT/prof" -name '*_stats.csv'); do cp "$f" "$OUT/"; done
       python3 tools/prof_steps.py "$OUT/prof" --steps 10 --out "$OUT/step_kernels.csv" > "$OUT/step_kernels.log" 2>&1 \
