@@ -604,6 +604,47 @@ size_t mx_jpeg_workspace(const mx_jpeg_info* info);
 int mx_jpeg_reconstruct(const int16_t* coefs, const mx_jpeg_info* info, void* ws, size_t ws_bytes, uint8_t* out,
                         int bgr, mx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Baseline JPEG encode (replaces the PIL / cv2.imwrite JPEG encode of build_corrupted_testsets.py
+ * and restore_testsets.py). Byte-identical to libjpeg-turbo behind PIL's
+ * Image.save(format="JPEG", quality=q, subsampling=s): SOI, JFIF APP0, two DQT, SOF0, four DHT (the
+ * T.81 K.3-K.6 tables), SOS, the scan, EOI. The encoder reuses mx_jpeg_info.
+ *   mx_jpeg_encode_info   host: geometry (as mx_jpeg_parse fills it), component ids 1,2,3, quantisation
+ *                         tables 0,1,1 = the Annex K tables scaled like jpeg_quality_scaling, the
+ *                         standard Huffman tables; scan_off = the header's length. subsampling in
+ *                         PIL's numbering: 0 = 4:4:4, 2 = 4:2:0. MX_EINVAL for another subsampling or
+ *                         a quality outside 1..100, MX_EUNSUPPORTED over 65535 a side or 2^28 pixels.
+ *   mx_jpeg_write_header  host: the marker segments up to and including SOS into out[cap]; *n = bytes
+ *                         (MX_EINVAL and the needed *n when cap is short; nothing past cap is written).
+ *   mx_jpeg_scan_bound    host: worst-case bytes of the entropy-coded segment of this geometry.
+ *   mx_jpeg_encode_coefs  host: sequential Huffman coding (jchuff.c) of natural-order int16
+ *                         coefficients [comp][by][bx][64] with the tables of `info` (parsed or from
+ *                         mx_jpeg_encode_info; 4:2:0 / 4:2:2 / 4:4:4 / grey): interleaved MCUs, DC
+ *                         differences per component, ZRL / EOB, 0xFF 0x00 stuffing, the last byte padded
+ *                         with ones. Writes the entropy-coded segment only (the caller appends EOI).
+ *                         MX_EUNSUPPORTED for restart_interval != 0; MX_EINVAL when cap is short (never
+ *                         written past) or a coefficient has no code. The CPU reference of, and the
+ *                         fallback for, mx_jpeg_entropy.
+ *   mx_jpeg_forward       device: uint8 pixels [height][width][3] (RGB, or BGR with bgr = 1) ->
+ *                         quantised coefficients in that layout, dummy blocks included: colour
+ *                         conversion, edge replication, h2v2 chroma downsampling, jpeg_fdct_islow and
+ *                         quantisation fused per MCU strip through LDS. 3 components, 4:4:4 or 4:2:0
+ *                         (MX_EUNSUPPORTED otherwise). coefs_dev 16-byte aligned, coef_total int16s.
+ *   mx_jpeg_entropy       device: the same bytes as mx_jpeg_encode_coefs into out_dev[out_cap], the
+ *                         length into *nbytes_dev (one int64; -1 when a coefficient has no code; a
+ *                         length over out_cap means the output was cut at out_cap). Multi-launch
+ *                         passes (bit counts, scans, bit scatter, 0xFF stuffing), no host
+ *                         synchronisation; ws: mx_jpeg_entropy_workspace() bytes, 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+int mx_jpeg_encode_info(int width, int height, int quality, int subsampling, mx_jpeg_info* out);
+int mx_jpeg_write_header(const mx_jpeg_info* info, uint8_t* out, int64_t cap, int64_t* n);
+int64_t mx_jpeg_scan_bound(const mx_jpeg_info* info);
+int mx_jpeg_encode_coefs(const mx_jpeg_info* info, const int16_t* coefs_host, uint8_t* out, int64_t cap, int64_t* n);
+int mx_jpeg_forward(const uint8_t* img, int bgr, const mx_jpeg_info* info, int16_t* coefs_dev, mx_stream_t stream);
+size_t mx_jpeg_entropy_workspace(const mx_jpeg_info* info);
+int mx_jpeg_entropy(const int16_t* coefs_dev, const mx_jpeg_info* info, void* ws, size_t ws_bytes, uint8_t* out_dev,
+                    int64_t out_cap, int64_t* nbytes_dev, mx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 // mx_jpeg.cpp — host half of the hybrid baseline-JPEG decoder: marker parsing and Huffman entropy
 // decoding into quantised DCT coefficients (the bitstream of a JPEG without restart markers is one
 // sequential prefix-code stream). The device half (mx_jpeg.hip) dequantises, runs the islow IDCT,
-// upsamples and converts colour.
+// upsamples and converts colour. The encoder's host half (tables, header, reference Huffman coder) is at
+// the end of the file.
 //
 // Replaces the libjpeg(-turbo) decode behind PIL Image.open(...).convert("RGB")
 // (coco_detection_dataset.py:23) and cv2.imread (restore_testsets.py:99, build_corrupted_testsets.py:139).
@@ -357,6 +358,315 @@ extern "C" int mx_jpeg_decode_coefs(const uint8_t* d, int64_t n, const mx_jpeg_i
         }
     }
     if (ri) --left;
+  }
+  return MX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Encoder, host half: the tables and header libjpeg writes for jpeg_set_defaults + jpeg_set_quality
+// (what PIL's Image.save(format="JPEG", quality, subsampling) produces), and the sequential Huffman
+// coder of jchuff.c over coefficients in the decoder's layout. The pixel stage (colour, downsampling,
+// forward DCT, quantisation) and the parallel entropy coder are in mx_jpeg.hip.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// T.81 Annex K.1 / K.2 base quantisation tables, natural order (jcparam.c std_luminance_quant_tbl)
+const uint8_t kBaseQ[2][64] = {
+    {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,
+     69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55,  64,
+     81, 104, 113, 92, 49, 64,  78,  87,  103, 121, 120, 101, 72, 92, 95,  98,  112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+     99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+
+// T.81 Annex K.3 - K.6 Huffman tables (jcparam.c std_huff_tables): BITS[1..16], HUFFVAL
+const uint8_t kStdDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
+                                   {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kStdAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125},
+                                   {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+const uint8_t kStdAcVal[2][162] = {
+    {1,   2,   3,   0,   4,   17,  5,   18,  33,  49,  65,  6,   19,  81,  97,  7,   34,  113, 20,  50,  129,
+     145, 161, 8,   35,  66,  177, 193, 21,  82,  209, 240, 36,  51,  98,  114, 130, 9,   10,  22,  23,  24,
+     25,  26,  37,  38,  39,  40,  41,  42,  52,  53,  54,  55,  56,  57,  58,  67,  68,  69,  70,  71,  72,
+     73,  74,  83,  84,  85,  86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116, 117,
+     118, 119, 120, 121, 122, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153,
+     154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186, 194, 195,
+     196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 225, 226, 227, 228, 229,
+     230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250},
+    {0,   1,   2,   3,   17,  4,   5,   33,  49,  6,   18,  65,  81,  7,   97,  113, 19,  34,  50,  129, 8,
+     20,  66,  145, 161, 177, 193, 9,   35,  51,  82,  240, 21,  98,  114, 209, 10,  22,  36,  52,  225, 37,
+     241, 23,  24,  25,  26,  38,  39,  40,  41,  42,  53,  54,  55,  56,  57,  58,  67,  68,  69,  70,  71,
+     72,  73,  74,  83,  84,  85,  86,  87,  88,  89,  90,  99,  100, 101, 102, 103, 104, 105, 106, 115, 116,
+     117, 118, 119, 120, 121, 122, 130, 131, 132, 133, 134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151,
+     152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186,
+     194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 226, 227, 228,
+     229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250}};
+
+// bounded byte sink: never writes at or past cap; `n` keeps counting so the caller learns the need
+struct Sink {
+  uint8_t* p;
+  int64_t cap, n = 0;
+  void put(int b) {
+    if (n < cap) p[n] = (uint8_t)b;
+    ++n;
+  }
+  void put2(int v) {
+    put(v >> 8);
+    put(v & 255);
+  }
+};
+
+int huff_total(const uint8_t* bits) {
+  int t = 0;
+  for (int l = 1; l <= 16; ++l) t += bits[l];
+  return t;
+}
+
+void write_header(const mx_jpeg_info* info, Sink& s) {
+  s.put2(0xFFD8);
+  s.put2(0xFFE0);  // APP0: JFIF 1.01, no units, 1:1 aspect, no thumbnail (jcmarker.c emit_jfif_app0)
+  s.put2(16);
+  const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+  for (int k = 0; k < 14; ++k) s.put(jfif[k]);
+  bool qdone[4] = {false, false, false, false};
+  for (int c = 0; c < info->ncomp; ++c) {  // one DQT segment per table, in order of first use, zig-zag
+    const int t = info->tq[c];
+    if (qdone[t]) continue;
+    qdone[t] = true;
+    s.put2(0xFFDB);
+    s.put2(67);
+    s.put(t);
+    for (int k = 0; k < 64; ++k) s.put(info->qt[t][kNatural[k]]);
+  }
+  s.put2(0xFFC0);
+  s.put2(8 + 3 * info->ncomp);
+  s.put(8);
+  s.put2(info->height);
+  s.put2(info->width);
+  s.put(info->ncomp);
+  for (int c = 0; c < info->ncomp; ++c) {
+    s.put(info->cid[c]);
+    s.put((info->h[c] << 4) | info->v[c]);
+    s.put(info->tq[c]);
+  }
+  bool hdone[8] = {false, false, false, false, false, false, false, false};
+  for (int c = 0; c < info->ncomp; ++c)  // DC then AC table of each component, once each (emit_dht)
+    for (int ac = 0; ac < 2; ++ac) {
+      const int t = ac ? 4 + info->ta[c] : info->td[c];
+      if (hdone[t]) continue;
+      hdone[t] = true;
+      const int tot = huff_total(info->hbits[t]);
+      s.put2(0xFFC4);
+      s.put2(19 + tot);
+      s.put(ac ? 0x10 | info->ta[c] : info->td[c]);
+      for (int l = 1; l <= 16; ++l) s.put(info->hbits[t][l]);
+      for (int k = 0; k < tot; ++k) s.put(info->hval[t][k]);
+    }
+  s.put2(0xFFDA);
+  s.put2(6 + 2 * info->ncomp);
+  s.put(info->ncomp);
+  for (int c = 0; c < info->ncomp; ++c) {
+    s.put(info->cid[c]);
+    s.put((info->td[c] << 4) | info->ta[c]);
+  }
+  s.put(0);
+  s.put(63);
+  s.put(0);
+}
+
+// what both coders need of an info, whoever filled it
+const char* enc_check(const mx_jpeg_info* info) {
+  if (!info) return "jpeg encode: null info";
+  if (info->ncomp != 1 && info->ncomp != 3) return "jpeg encode: 1 or 3 components";
+  if (info->width < 1 || info->height < 1 || info->mcux < 1 || info->mcuy < 1 || info->coef_total < 1)
+    return "jpeg encode: empty geometry (mx_jpeg_parse or mx_jpeg_encode_info first)";
+  int64_t off = 0;
+  for (int c = 0; c < info->ncomp; ++c) {
+    if (info->h[c] < 1 || info->h[c] > 2 || info->v[c] < 1 || info->v[c] > 2 || info->tq[c] < 0 || info->tq[c] > 3 ||
+        info->td[c] > 3 || info->ta[c] > 3)
+      return "jpeg encode: bad sampling factors or table numbers";
+    if (info->bw[c] != info->mcux * info->h[c] || info->bh[c] != info->mcuy * info->v[c] || info->coef_off[c] != off)
+      return "jpeg encode: inconsistent block geometry";
+    off += (int64_t)info->bw[c] * info->bh[c] * 64;
+  }
+  if (off != info->coef_total) return "jpeg encode: inconsistent coefficient total";
+  return nullptr;
+}
+
+struct BitSink {
+  Sink s;
+  uint64_t acc = 0;
+  int cnt = 0;
+  void put(uint32_t v, int n) {  // n <= 32 bits, MSB first; a 0x00 is stuffed after every 0xFF byte
+    acc = (acc << n) | v;
+    cnt += n;
+    while (cnt >= 8) {
+      const int b = (int)((acc >> (cnt - 8)) & 255);
+      s.put(b);
+      if (b == 255) s.put(0);
+      cnt -= 8;
+    }
+    acc &= ((uint64_t)1 << cnt) - 1;
+  }
+};
+
+inline int nbits_of(int a) { return a ? 32 - __builtin_clz((unsigned)a) : 0; }
+
+}  // namespace
+
+namespace mx {
+const char* jpeg_enc_check(const mx_jpeg_info* info) { return enc_check(info); }
+
+// Encoding table of one DHT table (T.81 C.2, jchuff.c jpeg_make_c_derived_tbl): tab[symbol] =
+// code << 8 | length, 0 for a symbol without a code. Shared with the device coder (mx_jpeg.hip).
+bool jpeg_enc_table(const uint8_t* bits, const uint8_t* vals, uint32_t* tab) {
+  if (!huff_counts_ok(bits) || huff_total(bits) > 256) return false;
+  memset(tab, 0, 256 * sizeof(uint32_t));
+  uint32_t code = 0;
+  int k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    for (int i = 0; i < bits[l]; ++i, ++k, ++code) {
+      if (tab[vals[k]]) return false;  // duplicate symbol
+      tab[vals[k]] = (code << 8) | (uint32_t)l;
+    }
+    code <<= 1;
+  }
+  return true;
+}
+}  // namespace mx
+
+extern "C" int mx_jpeg_encode_info(int width, int height, int quality, int subsampling, mx_jpeg_info* out) {
+  if (!out) return fail(MX_EINVAL, "jpeg_encode_info: null info");
+  if (width < 1 || height < 1) return fail(MX_EINVAL, "jpeg_encode_info: empty image");
+  if (quality < 1 || quality > 100) return fail(MX_EINVAL, "jpeg_encode_info: quality must be 1..100");
+  if (subsampling != 0 && subsampling != 2)
+    return fail(MX_EINVAL, "jpeg_encode_info: subsampling 0 (4:4:4) or 2 (4:2:0) only");
+  if (width > 65535 || height > 65535 || (int64_t)width * height > kMaxPixels)
+    return fail(MX_EUNSUPPORTED, "jpeg_encode_info: frame larger than 65535 a side or 2^28 pixels");
+  memset(out, 0, sizeof(*out));
+  out->width = width;
+  out->height = height;
+  out->ncomp = 3;
+  const int hm = subsampling == 2 ? 2 : 1;
+  out->hmax = out->vmax = hm;
+  out->mcux = cdiv(width, 8 * hm);
+  out->mcuy = cdiv(height, 8 * hm);
+  int64_t off = 0;
+  for (int c = 0; c < 3; ++c) {
+    out->cid[c] = (uint8_t)(c + 1);
+    out->h[c] = out->v[c] = c == 0 ? hm : 1;
+    out->tq[c] = out->td[c] = out->ta[c] = c == 0 ? 0 : 1;
+    out->bw[c] = out->mcux * out->h[c];
+    out->bh[c] = out->mcuy * out->v[c];
+    out->dw[c] = cdiv(width * out->h[c], hm);
+    out->dh[c] = cdiv(height * out->v[c], hm);
+    out->coef_off[c] = off;
+    off += (int64_t)out->bw[c] * out->bh[c] * 64;
+  }
+  out->coef_total = off;
+  // jcparam.c jpeg_quality_scaling + jpeg_add_quant_table (force_baseline)
+  const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 64; ++k) {
+      int q = (kBaseQ[t][k] * scale + 50) / 100;
+      out->qt[t][k] = (uint16_t)(q < 1 ? 1 : (q > 255 ? 255 : q));
+    }
+  for (int t = 0; t < 2; ++t) {
+    memcpy(&out->hbits[t][1], kStdDcBits[t], 16);
+    for (int k = 0; k < 12; ++k) out->hval[t][k] = (uint8_t)k;
+    memcpy(&out->hbits[4 + t][1], kStdAcBits[t], 16);
+    memcpy(out->hval[4 + t], kStdAcVal[t], 162);
+    out->hdef[t] = out->hdef[4 + t] = 1;
+  }
+  Sink s{nullptr, 0};
+  write_header(out, s);
+  out->scan_off = (int32_t)s.n;
+  return MX_OK;
+}
+
+extern "C" int mx_jpeg_write_header(const mx_jpeg_info* info, uint8_t* out, int64_t cap, int64_t* n) {
+  if (const char* e = enc_check(info)) return fail(MX_EINVAL, e);
+  if (!out || !n || cap < 0) return fail(MX_EINVAL, "jpeg_write_header: null argument");
+  for (int c = 0; c < info->ncomp; ++c)
+    for (int k = 0; k < 64; ++k)
+      if (info->qt[info->tq[c]][k] < 1 || info->qt[info->tq[c]][k] > 255)
+        return fail(MX_EUNSUPPORTED, "jpeg_write_header: 8-bit quantisation tables only");
+  Sink s{out, cap};
+  write_header(info, s);
+  *n = s.n;
+  if (s.n > cap) {
+    mx::set_error("jpeg_write_header: %lld bytes required, %lld given", (long long)s.n, (long long)cap);
+    return MX_EINVAL;
+  }
+  return MX_OK;
+}
+
+// Worst-case bytes of the entropy-coded segment: a block is at most 64 * 26 + 27 bits, every byte may
+// need a stuffed zero. Sizes the output of mx_jpeg_encode_coefs and of mx_jpeg_entropy.
+extern "C" int64_t mx_jpeg_scan_bound(const mx_jpeg_info* info) {
+  if (enc_check(info)) return 0;
+  const int64_t bits = (info->coef_total / 64) * (64 * 26 + 27);
+  return 2 * ((bits + 7) / 8 + 1);
+}
+
+extern "C" int mx_jpeg_encode_coefs(const mx_jpeg_info* info, const int16_t* coefs, uint8_t* out, int64_t cap,
+                                    int64_t* n) {
+  if (const char* e = enc_check(info)) return fail(MX_EINVAL, e);
+  if (!coefs || !out || !n || cap < 0) return fail(MX_EINVAL, "jpeg_encode_coefs: null argument");
+  if (info->restart_interval != 0) return fail(MX_EUNSUPPORTED, "jpeg_encode_coefs: restart intervals are not supported");
+  uint32_t dc[3][256], ac[3][256];
+  for (int c = 0; c < info->ncomp; ++c)
+    if (!mx::jpeg_enc_table(info->hbits[info->td[c]], info->hval[info->td[c]], dc[c]) ||
+        !mx::jpeg_enc_table(info->hbits[4 + info->ta[c]], info->hval[4 + info->ta[c]], ac[c]))
+      return fail(MX_EINVAL, "jpeg_encode_coefs: bad Huffman table");
+  BitSink b;
+  b.s = Sink{out, cap};
+  int pred[3] = {0, 0, 0};
+  const int64_t nmcu = (int64_t)info->mcux * info->mcuy;
+  for (int64_t mcu = 0; mcu < nmcu; ++mcu) {
+    const int64_t my = mcu / info->mcux, mx_ = mcu % info->mcux;
+    for (int c = 0; c < info->ncomp; ++c)
+      for (int vv = 0; vv < info->v[c]; ++vv)
+        for (int hh = 0; hh < info->h[c]; ++hh) {
+          const int64_t by = my * info->v[c] + vv, bx = mx_ * info->h[c] + hh;
+          const int16_t* blk = coefs + info->coef_off[c] + (by * info->bw[c] + bx) * 64;
+          // jchuff.c encode_one_block: DC difference, then (run, size) pairs over the zig-zag sequence
+          int d = blk[0] - pred[c];
+          pred[c] = blk[0];
+          int nb = nbits_of(d < 0 ? -d : d);
+          if (nb > 11 || !dc[c][nb]) return fail(MX_EINVAL, "jpeg_encode_coefs: DC difference without a code");
+          b.put(dc[c][nb] >> 8, (int)(dc[c][nb] & 255));
+          if (nb) b.put((uint32_t)(d < 0 ? d - 1 : d) & ((1u << nb) - 1), nb);
+          int r = 0;
+          for (int k = 1; k < 64; ++k) {
+            const int v = blk[kNatural[k]];
+            if (v == 0) {
+              ++r;
+              continue;
+            }
+            for (; r > 15; r -= 16) {
+              if (!ac[c][0xF0]) return fail(MX_EINVAL, "jpeg_encode_coefs: ZRL without a code");
+              b.put(ac[c][0xF0] >> 8, (int)(ac[c][0xF0] & 255));
+            }
+            nb = nbits_of(v < 0 ? -v : v);
+            const uint32_t e = nb > 10 ? 0 : ac[c][(r << 4) | nb];
+            if (!e) return fail(MX_EINVAL, "jpeg_encode_coefs: AC coefficient without a code");
+            b.put(e >> 8, (int)(e & 255));
+            b.put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << nb) - 1), nb);
+            r = 0;
+          }
+          if (r > 0) {
+            if (!ac[c][0]) return fail(MX_EINVAL, "jpeg_encode_coefs: EOB without a code");
+            b.put(ac[c][0] >> 8, (int)(ac[c][0] & 255));
+          }
+        }
+  }
+  if (b.cnt) b.put((1u << (8 - b.cnt)) - 1, 8 - b.cnt);  // flush_bits: pad the last byte with ones
+  *n = b.s.n;
+  if (b.s.n > cap) {
+    mx::set_error("jpeg_encode_coefs: %lld bytes required, %lld given (mx_jpeg_scan_bound is the worst case)",
+                  (long long)b.s.n, (long long)cap);
+    return MX_EINVAL;
   }
   return MX_OK;
 }

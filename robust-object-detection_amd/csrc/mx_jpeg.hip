@@ -1,4 +1,5 @@
-// mx_jpeg.hip — device half of the hybrid baseline-JPEG decoder (host half: mx_jpeg.cpp).
+// mx_jpeg.hip — device half of the hybrid baseline-JPEG decoder (host half: mx_jpeg.cpp), and below it
+// the device JPEG encoder (pixel stage + entropy coder).
 //
 // Reproduces libjpeg-turbo's default decompression (the decoder behind PIL and cv2.imread,
 // coco_detection_dataset.py:23, restore_testsets.py:99) bit for bit:
@@ -237,6 +238,671 @@ extern "C" int mx_jpeg_reconstruct(const int16_t* coefs, const mx_jpeg_info* inf
   MX_LAUNCH_CHECK();
   const int64_t np = (int64_t)j.width * j.height;
   jpeg_colour_kernel<<<(unsigned)cdiv(np, 256), 256, 0, st>>>((const uint8_t*)ws, j, bgr, out);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+// ================================================================================================
+// Encoder, device half. Reproduces libjpeg-turbo's default compression (PIL Image.save(format="JPEG",
+// quality, subsampling), cv2.imwrite) byte for byte:
+//   jpeg_forward_kernel   one workgroup per 64-pixel-wide strip of one MCU row (4 MCUs at 4:2:0, 8 at
+//                         4:4:4; 24 blocks either way), everything through LDS: 16-B pixel loads,
+//                         rgb_ycc_convert (jccolor.c, SCALEBITS 16), edge replication at full
+//                         resolution (jcprepct.c: columns to the block grid, rows only to an even
+//                         count), h2v2_downsample (jcsample.c, alternating 1/2 bias) with the
+//                         DOWNSAMPLED rows replicated to the iMCU height, jpeg_fdct_islow (jfdctint.c)
+//                         as a row pass and a column pass of 8 lanes per block, the quantiser of
+//                         jcdctmgr.c, the dummy blocks of jccoefct.c, 16-B coefficient stores.
+//   entropy passes        (a) jpeg_count_kernel: exact bit count of every block in scan order + scan
+//                         inside the workgroup; (b) jpeg_scan_bits_kernel: one workgroup scans the
+//                         workgroup sums; jpeg_zero_kernel clears the words the stream will occupy;
+//                         (c) jpeg_emit_kernel: every block writes its bits MSB first (atomicOr on the
+//                         words it shares with neighbours, 1-padding of the tail); (d) jpeg_ff_count /
+//                         jpeg_scan_ff / jpeg_stuff kernels: 0xFF bytes per 4-KiB chunk, scan, scatter
+//                         with the stuffed 0x00. No pass waits on another workgroup; every launch is
+//                         sized on the host from the worst case and exits early on the device total.
+// ================================================================================================
+namespace mx {
+
+bool jpeg_enc_table(const uint8_t* bits, const uint8_t* vals, uint32_t* tab);  // mx_jpeg.cpp
+
+struct JpegFwd {
+  int32_t width, height, mcux, bgr;
+  int32_t bw[3];
+  int32_t wib0, hib0;  // luma blocks that hold image samples, across / down
+  int64_t coef_off[3];
+  uint16_t qt[3][64];  // per component
+};
+
+template <int PASS>
+__device__ __forceinline__ void fdct8(const int* d, int* o) {
+  const int s = PASS == 0 ? 11 : 15;  // CONST_BITS -/+ PASS1_BITS
+  int tmp0 = d[0] + d[7], tmp7 = d[0] - d[7], tmp1 = d[1] + d[6], tmp6 = d[1] - d[6];
+  int tmp2 = d[2] + d[5], tmp5 = d[2] - d[5], tmp3 = d[3] + d[4], tmp4 = d[3] - d[4];
+  const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  if (PASS == 0) {
+    o[0] = (tmp10 + tmp11) << 2;
+    o[4] = (tmp10 - tmp11) << 2;
+  } else {
+    o[0] = (tmp10 + tmp11 + 2) >> 2;
+    o[4] = (tmp10 - tmp11 + 2) >> 2;
+  }
+  int z1 = (tmp12 + tmp13) * FIX_0_541196100;
+  o[2] = (z1 + tmp13 * FIX_0_765366865 + (1 << (s - 1))) >> s;
+  o[6] = (z1 + tmp12 * (-FIX_1_847759065) + (1 << (s - 1))) >> s;
+  z1 = tmp4 + tmp7;
+  int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+  const int z5 = (z3 + z4) * FIX_1_175875602;
+  tmp4 *= FIX_0_298631336;
+  tmp5 *= FIX_2_053119869;
+  tmp6 *= FIX_3_072711026;
+  tmp7 *= FIX_1_501321110;
+  z1 *= -FIX_0_899976223;
+  z2 *= -FIX_2_562915447;
+  z3 = z3 * (-FIX_1_961570560) + z5;
+  z4 = z4 * (-FIX_0_390180644) + z5;
+  o[7] = (tmp4 + z1 + z3 + (1 << (s - 1))) >> s;
+  o[5] = (tmp5 + z2 + z4 + (1 << (s - 1))) >> s;
+  o[3] = (tmp6 + z2 + z3 + (1 << (s - 1))) >> s;
+  o[1] = (tmp7 + z1 + z4 + (1 << (s - 1))) >> s;
+}
+
+constexpr int kFwdBlocks = 24;  // blocks per workgroup: 16 + 4 + 4 (4:2:0) or 8 + 8 + 8 (4:4:4)
+constexpr int kRawPitch = 224;  // 64 pixels * 3 + up to 15 bytes of misalignment, in 16-B chunks
+
+// block b of the workgroup's tile -> component, plane row of its first sample, plane column
+template <int SUB>
+__device__ __forceinline__ void fwd_block(int b, int& c, int& row0, int& col0) {
+  if (SUB == 2) {
+    if (b < 16) {
+      c = 0;
+      row0 = (b >> 3) * 8;
+      col0 = (b & 7) * 8;
+    } else {
+      c = 1 + ((b - 16) >> 2);
+      row0 = 0;
+      col0 = ((b - 16) & 3) * 8;
+    }
+  } else {
+    c = b >> 3;
+    row0 = 0;
+    col0 = (b & 7) * 8;
+  }
+}
+
+// SUB 2: 4:2:0 (luma 2x2 blocks per MCU), SUB 1: 4:4:4
+template <int SUB>
+__global__ void __launch_bounds__(256) jpeg_forward_kernel(const uint8_t* __restrict__ img, JpegFwd j,
+                                                           int16_t* __restrict__ coefs) {
+  constexpr int ROWS = 8 * SUB;  // pixel rows of the tile
+  constexpr int G = SUB == 2 ? 4 : 8;  // MCUs of the tile
+  __shared__ __attribute__((aligned(16))) uint8_t raw[16 * kRawPitch];
+  __shared__ __attribute__((aligned(16))) uint8_t pl[3][16][64];
+  __shared__ int ws[kFwdBlocks * 72];  // pass-1 output, block pitch 72 words: the 8 blocks of a wave hit 8 bank groups
+  __shared__ __attribute__((aligned(16))) int16_t outc[kFwdBlocks * 64];
+  __shared__ uint16_t qd[3][64];
+  const int t = threadIdx.x;
+  const int tx = blockIdx.x, my = blockIdx.y;
+  const int x0 = tx * 64, y0 = my * ROWS;
+  const int xmax = min(63, j.width - 1 - x0), rmax = min(ROWS - 1, j.height - 1 - y0);
+  if (t < 192) qd[t >> 6][t & 63] = j.qt[t >> 6][t & 63];
+  // ---- pixels -> LDS in 16-B chunks aligned in memory; chunks that straddle the tensor go by bytes
+  const uintptr_t base = (uintptr_t)img, end = base + (uintptr_t)j.width * j.height * 3;
+  {
+    const int r = t / 14, ch = t % 14;
+    if (r <= rmax) {
+      const uintptr_t a = base + ((uintptr_t)(y0 + r) * j.width + x0) * 3;
+      const uintptr_t stop = a + (uintptr_t)(xmax + 1) * 3;
+      const uintptr_t p = (a & ~(uintptr_t)15) + 16 * ch;
+      if (p < stop) {
+        uint4 v;
+        if (p >= base && p + 16 <= end) {
+          v = *(const uint4*)p;
+        } else {
+          uint8_t* vb = (uint8_t*)&v;
+#pragma unroll
+          for (int k = 0; k < 16; ++k) vb[k] = (p + k >= base && p + k < end) ? *(const uint8_t*)(p + k) : 0;
+        }
+        *(uint4*)&raw[r * kRawPitch + 16 * ch] = v;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- colour conversion (+ chroma downsampling) into the component planes
+  auto px = [&](int r, int x, int& R, int& Gc, int& B) {
+    const int off = (int)((base + ((uintptr_t)(y0 + r) * j.width + x0) * 3) & 15);
+    const uint8_t* p = &raw[r * kRawPitch + off + 3 * x];
+    R = p[j.bgr ? 2 : 0];
+    Gc = p[1];
+    B = p[j.bgr ? 0 : 2];
+  };
+  if (SUB == 2) {
+    const int qy = t >> 5, qx = t & 31;
+    // luma: rows and columns beyond the image replicate the last one
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        int R, Gc, B;
+        px(min(2 * qy + dy, rmax), min(2 * qx + dx, xmax), R, Gc, B);
+        pl[0][2 * qy + dy][2 * qx + dx] = (uint8_t)((19595 * R + 38470 * Gc + 7471 * B + 32768) >> 16);
+      }
+    // chroma: the last DOWNSAMPLED row is the one replicated; inside it an odd image height repeats
+    // the last pixel row
+    const int cy = min(y0 / 2 + qy, (j.height + 1) / 2 - 1);
+    const int ra = 2 * cy - y0;
+    int cb = 0, cr = 0;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        int R, Gc, B;
+        px(min(ra + dy, rmax), min(2 * qx + dx, xmax), R, Gc, B);
+        cb += (-11059 * R - 21709 * Gc + 32768 * B + (128 << 16) + 32767) >> 16;
+        cr += (32768 * R - 27439 * Gc - 5329 * B + (128 << 16) + 32767) >> 16;
+      }
+    const int bias = 1 + (qx & 1);
+    pl[1][qy][qx] = (uint8_t)((cb + bias) >> 2);
+    pl[2][qy][qx] = (uint8_t)((cr + bias) >> 2);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int p = t + 256 * k, r = p >> 6, x = p & 63;
+      int R, Gc, B;
+      px(min(r, rmax), min(x, xmax), R, Gc, B);
+      pl[0][r][x] = (uint8_t)((19595 * R + 38470 * Gc + 7471 * B + 32768) >> 16);
+      pl[1][r][x] = (uint8_t)((-11059 * R - 21709 * Gc + 32768 * B + (128 << 16) + 32767) >> 16);
+      pl[2][r][x] = (uint8_t)((32768 * R - 27439 * Gc - 5329 * B + (128 << 16) + 32767) >> 16);
+    }
+  }
+  __syncthreads();
+  // ---- jpeg_fdct_islow pass 1: one block row per lane
+  const int b = t >> 3, l = t & 7;
+  int c = 0, row0 = 0, col0 = 0;
+  if (b < kFwdBlocks) {
+    fwd_block<SUB>(b, c, row0, col0);
+    const uint2 s = *(const uint2*)&pl[c][row0 + l][col0];
+    int d[8], o[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      d[k] = (int)((s.x >> (8 * k)) & 255) - 128;
+      d[k + 4] = (int)((s.y >> (8 * k)) & 255) - 128;
+    }
+    fdct8<0>(d, o);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ws[b * 72 + l * 8 + k] = o[k];
+  }
+  __syncthreads();
+  // ---- pass 2: one block column per lane, then quantisation (jcdctmgr.c: divisor 8 * q)
+  if (b < kFwdBlocks) {
+    int d[8], o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = ws[b * 72 + k * 8 + l];
+    fdct8<1>(d, o);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int dv = 8 * (int)qd[c][k * 8 + l];
+      const int a = (o[k] < 0 ? -o[k] : o[k]) + (dv >> 1);
+      const int q = a >= dv ? a / dv : 0;
+      outc[b * 64 + k * 8 + l] = (int16_t)(o[k] < 0 ? -q : q);
+    }
+  }
+  __syncthreads();
+  // ---- dummy luma blocks of an edge MCU (jccoefct.c compress_data): AC zero, DC of the block
+  // before it in the MCU
+  if (SUB == 2 && t < G && tx * G + t < j.mcux) {
+    for (int k = 1; k < 4; ++k) {
+      const int vv = k >> 1, hh = k & 1;
+      if (2 * (tx * G + t) + hh >= j.wib0 || 2 * my + vv >= j.hib0) {
+        const int pv = k - 1;
+        int16_t* blk = &outc[(vv * 8 + 2 * t + hh) * 64];
+        const int16_t dc = outc[((pv >> 1) * 8 + 2 * t + (pv & 1)) * 64];
+        for (int e = 0; e < 64; ++e) blk[e] = 0;
+        blk[0] = dc;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- 16-B stores; the blocks of one component row are contiguous in [comp][by][bx][64]
+  if (b < kFwdBlocks) {
+    const int by = SUB == 2 && c == 0 ? 2 * my + (row0 >> 3) : my;
+    const int bx = (SUB == 2 && c != 0 ? tx * 4 : tx * 8) + (col0 >> 3);
+    if (bx < j.bw[c])
+      *(uint4*)(coefs + j.coef_off[c] + ((int64_t)by * j.bw[c] + bx) * 64 + l * 8) = *(const uint4*)&outc[b * 64 + l * 8];
+  }
+}
+
+// ---------------------------------------------------------------- entropy coder
+struct JpegScan {
+  int32_t ncomp, mcux, bpm;
+  int32_t h[3], v[3], bw[3], first[3];  // first: index of the component's first block inside an MCU
+  int64_t coef_off[3];
+  int64_t nblk;  // blocks of the scan
+};
+struct JpegHuff {
+  uint32_t dc[3][16], ac[3][256];  // per component: code << 8 | length (0: no code)
+};
+constexpr int kHuffWords = 3 * 16 + 3 * 256;
+constexpr int kMaxBlockBits = 64 * 26 + 27;
+constexpr int kChunk = 4096;  // bytes per workgroup of the stuffing passes (16 per lane)
+
+__device__ constexpr int kZig[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,
+                                     12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
+                                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
+                                     58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+__device__ __forceinline__ int sel3(const int32_t* a, int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : a[2]); }
+
+// scan-order block s -> component, coefficient offset of the block and of the block whose DC is its
+// predictor (-1: none, the first block of the component)
+__device__ __forceinline__ void scan_locate(const JpegScan& j, int64_t s, int& c, int64_t& off, int64_t& poff) {
+  int64_t m = s / j.bpm;
+  const int k = (int)(s - m * j.bpm);
+  c = (j.ncomp == 3 && k >= j.first[1]) ? (k >= j.first[2] ? 2 : 1) : 0;
+  const int h = sel3(j.h, c), v = sel3(j.v, c), bw = sel3(j.bw, c);
+  const int64_t co = c == 0 ? j.coef_off[0] : (c == 1 ? j.coef_off[1] : j.coef_off[2]);
+  int kk = k - sel3(j.first, c);
+  off = co + (((m / j.mcux) * v + kk / h) * bw + (m % j.mcux) * h + kk % h) * 64;
+  if (kk > 0) {
+    --kk;
+  } else if (m > 0) {
+    --m;
+    kk = h * v - 1;
+  } else {
+    poff = -1;
+    return;
+  }
+  poff = co + (((m / j.mcux) * v + kk / h) * bw + (m % j.mcux) * h + kk % h) * 64;
+}
+
+struct BitCount {
+  uint32_t bits = 0;
+  __device__ __forceinline__ void put(uint32_t, int n) { bits += n; }
+};
+
+// MSB-first writer into 32-bit words (byte i of the stream is bits 31-8*(i%4).. of word i/4). The
+// first and the last word of a block may be shared with its neighbours: atomicOr into the zeroed
+// buffer; the words between belong to this block alone.
+struct BitEmit {
+  uint32_t* words;
+  int64_t w, cap;
+  uint64_t acc = 0;
+  int nacc;
+  bool first = true;
+  __device__ __forceinline__ void put(uint32_t v, int n) {  // 0 <= n <= 27, nacc < 32
+    if (n == 0) return;
+    acc |= (uint64_t)v << (64 - nacc - n);
+    nacc += n;
+    if (nacc >= 32) {
+      const uint32_t x = (uint32_t)(acc >> 32);
+      if (w < cap) {
+        if (first) atomicOr(&words[w], x);
+        else words[w] = x;
+      }
+      first = false;
+      ++w;
+      acc <<= 32;
+      nacc -= 32;
+    }
+  }
+  __device__ __forceinline__ void finish() {
+    if (nacc > 0 && w < cap) atomicOr(&words[w], (uint32_t)(acc >> 32));
+  }
+};
+
+// jchuff.c encode_one_block on one block (natural order, 8 x 16 B); false when a value has no code
+// (the bits then written stay inside the kMaxBlockBits bound: sizes are clamped to 11 / 10)
+template <typename S>
+__device__ __forceinline__ bool encode_block(const int16_t* blk, int pred, const uint32_t* dct, const uint32_t* act,
+                                             S& s) {
+  uint32_t w[32];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint4 u = ((const uint4*)blk)[i];
+    w[4 * i] = u.x;
+    w[4 * i + 1] = u.y;
+    w[4 * i + 2] = u.z;
+    w[4 * i + 3] = u.w;
+  }
+  bool ok = true;
+  {
+    const int d = (int)(int16_t)(w[0] & 0xffff) - pred;
+    int nb = 32 - __clz(d < 0 ? -d : d);
+    if (nb > 11) {
+      ok = false;
+      nb = 11;
+    }
+    const uint32_t e = dct[nb];
+    ok = ok && e != 0;
+    s.put(((e >> 8) << nb) | ((uint32_t)(d < 0 ? d - 1 : d) & ((1u << nb) - 1)), (int)(e & 255) + nb);
+  }
+  int r = 0;
+#pragma unroll
+  for (int k = 1; k < 64; ++k) {
+    const int n = kZig[k];
+    const int v = (int)(int16_t)((w[n >> 1] >> ((n & 1) * 16)) & 0xffff);
+    if (v == 0) {
+      ++r;
+    } else {
+      if (r > 15) {
+        const uint32_t z = act[0xF0];
+        ok = ok && z != 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+          if (i < (r >> 4)) s.put(z >> 8, (int)(z & 255));
+        r &= 15;
+      }
+      int nb = 32 - __clz(v < 0 ? -v : v);
+      if (nb > 10) {
+        ok = false;
+        nb = 10;
+      }
+      const uint32_t e = act[(r << 4) | nb];
+      ok = ok && e != 0;
+      s.put(((e >> 8) << nb) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << nb) - 1)), (int)(e & 255) + nb);
+      r = 0;
+    }
+  }
+  if (r > 0) {
+    const uint32_t e = act[0];
+    ok = ok && e != 0;
+    s.put(e >> 8, (int)(e & 255));
+  }
+  return ok;
+}
+
+// exclusive scan over the N lanes of a workgroup (sh: N words); *total = the sum
+template <int N>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* sh, uint32_t* total) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int o = 1; o < N; o <<= 1) {
+    const uint32_t a = t >= o ? sh[t - o] : 0;
+    __syncthreads();
+    sh[t] += a;
+    __syncthreads();
+  }
+  const uint32_t inc = sh[t];
+  *total = sh[N - 1];
+  __syncthreads();
+  return inc - v;
+}
+
+__device__ __forceinline__ void load_huff(const JpegHuff& hd, uint32_t* sh) {
+  const uint32_t* src = (const uint32_t*)&hd;
+  for (int i = threadIdx.x; i < kHuffWords; i += blockDim.x) sh[i] = src[i];
+  __syncthreads();
+}
+
+// (a) bits of every block + exclusive scan inside the workgroup of 256 blocks
+__global__ void __launch_bounds__(256) jpeg_count_kernel(const int16_t* __restrict__ coefs, JpegScan j, JpegHuff hd,
+                                                         uint32_t* __restrict__ local, uint32_t* __restrict__ wg_sum,
+                                                         int64_t* __restrict__ scal) {
+  __shared__ uint32_t huff[kHuffWords];
+  __shared__ uint32_t sh[256];
+  load_huff(hd, huff);
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t bits = 0;
+  if (s < j.nblk) {
+    int c;
+    int64_t off, poff;
+    scan_locate(j, s, c, off, poff);
+    BitCount bc;
+    if (!encode_block(coefs + off, poff < 0 ? 0 : (int)coefs[poff], huff + 16 * c, huff + 48 + 256 * c, bc))
+      atomicOr((unsigned long long*)&scal[1], 1ull);
+    bits = bc.bits;
+  }
+  uint32_t total;
+  const uint32_t ex = block_excl_scan<256>(bits, sh, &total);
+  if (s < j.nblk) local[s] = ex;
+  if (threadIdx.x == 0) wg_sum[blockIdx.x] = total;
+}
+
+// one workgroup: out[i] = sum of in[0..i), *total = sum of all n
+__device__ __forceinline__ int64_t scan_partials(const uint32_t* in, int64_t n, int64_t* out, uint32_t* sh) {
+  int64_t carry = 0;
+  for (int64_t base = 0; base < n; base += 1024) {
+    const int64_t i = base + threadIdx.x;
+    uint32_t total;
+    const uint32_t ex = block_excl_scan<1024>(i < n ? in[i] : 0, sh, &total);
+    if (i < n) out[i] = carry + ex;
+    carry += total;
+  }
+  return carry;
+}
+
+// (b) scal[0] = bits of the scan
+__global__ void __launch_bounds__(1024) jpeg_scan_bits_kernel(const uint32_t* __restrict__ wg_sum, int64_t n,
+                                                              int64_t* __restrict__ wg_off, int64_t* __restrict__ scal) {
+  __shared__ uint32_t sh[1024];
+  const int64_t total = scan_partials(wg_sum, n, wg_off, sh);
+  if (threadIdx.x == 0) scal[0] = total;
+}
+
+// bytes of the unstuffed stream (the last one padded)
+__device__ __forceinline__ int64_t stream_bytes(const int64_t* scal) { return (scal[0] + 7) >> 3; }
+
+__global__ void __launch_bounds__(256) jpeg_zero_kernel(uint32_t* __restrict__ words, int64_t cap,
+                                                        const int64_t* __restrict__ scal) {
+  int64_t n = ((stream_bytes(scal) + 15) >> 4) << 2;  // whole 16-B groups: what the stuffing lanes read
+  n = n < cap ? n : cap;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) words[i] = 0;
+}
+
+// (c) every block writes its bits at its offset
+__global__ void __launch_bounds__(256) jpeg_emit_kernel(const int16_t* __restrict__ coefs, JpegScan j, JpegHuff hd,
+                                                        const uint32_t* __restrict__ local,
+                                                        const int64_t* __restrict__ wg_off, uint32_t* __restrict__ words,
+                                                        int64_t cap) {
+  __shared__ uint32_t huff[kHuffWords];
+  load_huff(hd, huff);
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= j.nblk) return;
+  int c;
+  int64_t off, poff;
+  scan_locate(j, s, c, off, poff);
+  const int64_t pos = wg_off[blockIdx.x] + local[s];
+  BitEmit be;
+  be.words = words;
+  be.cap = cap;
+  be.w = pos >> 5;
+  be.nacc = (int)(pos & 31);
+  encode_block(coefs + off, poff < 0 ? 0 : (int)coefs[poff], huff + 16 * c, huff + 48 + 256 * c, be);
+  if (s == j.nblk - 1) {  // flush_bits: ones up to the byte boundary
+    const int pad = (8 - (be.nacc & 7)) & 7;
+    be.put((1u << pad) - 1, pad);
+  }
+  be.finish();
+}
+
+// the 16 stream bytes of lane `g` (g-th group of 16) and how many are 0xFF; bytes at or past nb are not counted
+__device__ __forceinline__ int ff_group(const uint32_t* words, int64_t g, int64_t nb, uint32_t (&w)[4]) {
+  int n = 0;
+  if (g * 16 < nb) {
+    const uint4 u = ((const uint4*)words)[g];
+    w[0] = u.x, w[1] = u.y, w[2] = u.z, w[3] = u.w;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      n += (g * 16 + k < nb) && ((w[k >> 2] >> (24 - 8 * (k & 3))) & 255) == 255;
+  }
+  return n;
+}
+
+// (d1) 0xFF bytes per chunk
+__global__ void __launch_bounds__(256) jpeg_ff_count_kernel(const uint32_t* __restrict__ words,
+                                                            const int64_t* __restrict__ scal,
+                                                            uint32_t* __restrict__ wg_ff) {
+  __shared__ uint32_t sh[256];
+  const int64_t nb = stream_bytes(scal);
+  if ((int64_t)blockIdx.x * kChunk >= nb) return;
+  uint32_t w[4];
+  const int n = ff_group(words, (int64_t)blockIdx.x * 256 + threadIdx.x, nb, w);
+  uint32_t total;
+  block_excl_scan<256>(n, sh, &total);
+  if (threadIdx.x == 0) wg_ff[blockIdx.x] = total;
+}
+
+// (d2) chunk offsets; *nbytes = stuffed length, or -1 when a coefficient had no code
+__global__ void __launch_bounds__(1024) jpeg_scan_ff_kernel(const uint32_t* __restrict__ wg_ff,
+                                                            const int64_t* __restrict__ scal,
+                                                            int64_t* __restrict__ wg_ffoff, int64_t* __restrict__ nbytes) {
+  __shared__ uint32_t sh[1024];
+  const int64_t nb = stream_bytes(scal);
+  const int64_t ff = scan_partials(wg_ff, (nb + kChunk - 1) / kChunk, wg_ffoff, sh);
+  if (threadIdx.x == 0) *nbytes = scal[1] ? -1 : nb + ff;
+}
+
+// (d3) scatter with the stuffed zeros
+__global__ void __launch_bounds__(256) jpeg_stuff_kernel(const uint32_t* __restrict__ words,
+                                                         const int64_t* __restrict__ scal,
+                                                         const int64_t* __restrict__ wg_ffoff, uint8_t* __restrict__ out,
+                                                         int64_t out_cap) {
+  __shared__ uint32_t sh[256];
+  const int64_t nb = stream_bytes(scal);
+  if ((int64_t)blockIdx.x * kChunk >= nb) return;
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t w[4];
+  const int n = ff_group(words, g, nb, w);
+  uint32_t total;
+  const uint32_t ex = block_excl_scan<256>(n, sh, &total);
+  if (g * 16 >= nb) return;
+  int64_t pos = g * 16 + wg_ffoff[blockIdx.x] + ex;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (g * 16 + k < nb) {
+      const uint32_t b = (w[k >> 2] >> (24 - 8 * (k & 3))) & 255;
+      if (pos < out_cap) out[pos] = (uint8_t)b;
+      ++pos;
+      if (b == 255) {
+        if (pos < out_cap) out[pos] = 0;
+        ++pos;
+      }
+    }
+  }
+}
+
+struct EntropyWs {
+  uint32_t *local, *wg_sum, *words, *wg_ff;
+  int64_t *wg_off, *scal, *wg_ffoff;
+  int64_t nblk, nwg, wcap, nchunk;
+  size_t bytes;
+};
+
+static EntropyWs entropy_ws(const mx_jpeg_info* info, void* ws, size_t cap) {
+  EntropyWs e;
+  e.nblk = info->coef_total / 64;
+  e.nwg = cdiv(e.nblk, 256);
+  e.wcap = cdiv(cdiv(e.nblk * kMaxBlockBits, 8), 16) * 4 + 4;  // whole 16-B groups
+  e.nchunk = cdiv(e.wcap * 4, kChunk);
+  Carver cv(ws, cap);
+  e.local = cv.take<uint32_t>(e.nblk);
+  e.wg_sum = cv.take<uint32_t>(e.nwg);
+  e.wg_off = cv.take<int64_t>(e.nwg);
+  e.scal = cv.take<int64_t>(4);
+  e.words = cv.take<uint32_t>(e.wcap);
+  e.wg_ff = cv.take<uint32_t>(e.nchunk);
+  e.wg_ffoff = cv.take<int64_t>(e.nchunk);
+  e.bytes = align_up(cv.off);
+  return e;
+}
+
+const char* jpeg_enc_check(const mx_jpeg_info* info);  // mx_jpeg.cpp: geometry both coders rely on
+
+}  // namespace mx
+
+extern "C" int mx_jpeg_forward(const uint8_t* img, int bgr, const mx_jpeg_info* info, int16_t* coefs,
+                               mx_stream_t stream) {
+  MX_CHECK_ARG(img && info && coefs, "jpeg_forward: null argument");
+  const char* bad = jpeg_enc_check(info);
+  MX_CHECK_ARG(!bad, "jpeg_forward: %s", bad);
+  MX_CHECK_ARG(((uintptr_t)coefs & 15) == 0, "jpeg_forward: coefficients must be 16-byte aligned");
+  const bool c11 = info->ncomp == 3 && info->h[1] == 1 && info->v[1] == 1 && info->h[2] == 1 && info->v[2] == 1;
+  const int sub = c11 && info->h[0] == 2 && info->v[0] == 2 ? 2 : (c11 && info->h[0] == 1 && info->v[0] == 1 ? 1 : 0);
+  if (!sub) {
+    set_error("jpeg_forward: 3-component 4:4:4 or 4:2:0 only");
+    return MX_EUNSUPPORTED;
+  }
+  MX_CHECK_ARG(info->mcux == cdiv(info->width, 8 * sub) && info->mcuy == cdiv(info->height, 8 * sub),
+               "jpeg_forward: MCU counts do not match the image size");
+  JpegFwd j;
+  j.width = info->width;
+  j.height = info->height;
+  j.mcux = info->mcux;
+  j.bgr = bgr ? 1 : 0;
+  j.wib0 = (int)cdiv(info->width, 8);
+  j.hib0 = (int)cdiv(info->height, 8);
+  for (int c = 0; c < 3; ++c) {
+    j.bw[c] = info->bw[c];
+    j.coef_off[c] = info->coef_off[c];
+    for (int k = 0; k < 64; ++k) {
+      MX_CHECK_ARG(info->qt[info->tq[c]][k] >= 1, "jpeg_forward: zero quantiser");
+      j.qt[c][k] = info->qt[info->tq[c]][k];
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)cdiv(info->mcux, sub == 2 ? 4 : 8), (unsigned)info->mcuy);
+  if (sub == 2) jpeg_forward_kernel<2><<<grid, 256, 0, st>>>(img, j, coefs);
+  else jpeg_forward_kernel<1><<<grid, 256, 0, st>>>(img, j, coefs);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+extern "C" size_t mx_jpeg_entropy_workspace(const mx_jpeg_info* info) {
+  if (jpeg_enc_check(info)) return 0;
+  return entropy_ws(info, nullptr, 0).bytes;
+}
+
+extern "C" int mx_jpeg_entropy(const int16_t* coefs, const mx_jpeg_info* info, void* ws, size_t ws_bytes, uint8_t* out,
+                               int64_t out_cap, int64_t* nbytes, mx_stream_t stream) {
+  MX_CHECK_ARG(coefs && info && ws && out && nbytes && out_cap >= 0, "jpeg_entropy: null argument");
+  const char* bad = jpeg_enc_check(info);
+  MX_CHECK_ARG(!bad, "jpeg_entropy: %s", bad);
+  MX_CHECK_ARG(((uintptr_t)coefs & 15) == 0 && ((uintptr_t)ws & 255) == 0,
+               "jpeg_entropy: coefficients must be 16-byte and the workspace 256-byte aligned");
+  if (info->restart_interval != 0) {
+    set_error("jpeg_entropy: restart intervals are not supported");
+    return MX_EUNSUPPORTED;
+  }
+  const EntropyWs e = entropy_ws(info, ws, ws_bytes);
+  MX_CHECK_ARG(e.bytes <= ws_bytes, "jpeg_entropy: workspace of %lld bytes required", (long long)e.bytes);
+  JpegScan j;
+  JpegHuff hd;
+  j.ncomp = info->ncomp;
+  j.mcux = info->mcux;
+  j.nblk = e.nblk;
+  j.bpm = 0;
+  for (int c = 0; c < 3; ++c) {
+    const bool on = c < info->ncomp;
+    j.h[c] = on ? info->h[c] : 1;
+    j.v[c] = on ? info->v[c] : 1;
+    j.bw[c] = on ? info->bw[c] : 0;
+    j.coef_off[c] = on ? info->coef_off[c] : 0;
+    j.first[c] = j.bpm;
+    if (on) j.bpm += info->h[c] * info->v[c];
+    uint32_t tab[256];
+    const int cc = on ? c : 0;
+    MX_CHECK_ARG(jpeg_enc_table(info->hbits[info->td[cc]], info->hval[info->td[cc]], tab), "jpeg_entropy: bad DC Huffman table");
+    for (int k = 0; k < 16; ++k) hd.dc[c][k] = tab[k];
+    MX_CHECK_ARG(jpeg_enc_table(info->hbits[4 + info->ta[cc]], info->hval[4 + info->ta[cc]], hd.ac[c]),
+                 "jpeg_entropy: bad AC Huffman table");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  MX_HIP(hipMemsetAsync(e.scal, 0, 4 * sizeof(int64_t), st));
+  jpeg_count_kernel<<<(unsigned)e.nwg, 256, 0, st>>>(coefs, j, hd, e.local, e.wg_sum, e.scal);
+  MX_LAUNCH_CHECK();
+  jpeg_scan_bits_kernel<<<1, 1024, 0, st>>>(e.wg_sum, e.nwg, e.wg_off, e.scal);
+  MX_LAUNCH_CHECK();
+  jpeg_zero_kernel<<<(unsigned)(e.wcap / 256 < 2048 ? e.wcap / 256 + 1 : 2048), 256, 0, st>>>(e.words, e.wcap, e.scal);
+  MX_LAUNCH_CHECK();
+  jpeg_emit_kernel<<<(unsigned)e.nwg, 256, 0, st>>>(coefs, j, hd, e.local, e.wg_off, e.words, e.wcap);
+  MX_LAUNCH_CHECK();
+  jpeg_ff_count_kernel<<<(unsigned)e.nchunk, 256, 0, st>>>(e.words, e.scal, e.wg_ff);
+  MX_LAUNCH_CHECK();
+  jpeg_scan_ff_kernel<<<1, 1024, 0, st>>>(e.wg_ff, e.scal, e.wg_ffoff, nbytes);
+  MX_LAUNCH_CHECK();
+  jpeg_stuff_kernel<<<(unsigned)e.nchunk, 256, 0, st>>>(e.words, e.scal, e.wg_ffoff, out, out_cap);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

@@ -107,6 +107,13 @@ _SIGS = {
     "mx_jpeg_decode_coefs": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "mx_jpeg_workspace": (c_sz, [c_vp]),
     "mx_jpeg_reconstruct": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "mx_jpeg_encode_info": (c_int, [c_int, c_int, c_int, c_int, c_vp]),
+    "mx_jpeg_write_header": (c_int, [c_vp, c_vp, c_i64, c_vp]),
+    "mx_jpeg_scan_bound": (c_i64, [c_vp]),
+    "mx_jpeg_encode_coefs": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "mx_jpeg_forward": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
+    "mx_jpeg_entropy_workspace": (c_sz, [c_vp]),
+    "mx_jpeg_entropy": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_i64, c_vp, c_vp]),
     "mx_conv_set_wgrad_variant": (c_int, [c_int]),
     "mx_conv_get_wgrad_variant": (c_int, []),
     "mx_conv_set_wgrad_target": (c_int, [c_i64]),

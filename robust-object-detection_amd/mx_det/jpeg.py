@@ -7,6 +7,9 @@ dequantises, runs the libjpeg islow IDCT, upsamples the chroma and converts YCbC
 decode -- PIL Image.open(p).convert("RGB") (coco_detection_dataset.py:23), or with bgr=True
 cv2.imread (restore_testsets.py:99). Progressive / arithmetic / CMYK / 4:4:0 files raise
 NotImplementedError (MX_EUNSUPPORTED); callers that must accept them decode those on the host.
+
+Encode (encode / write_file / encode_coefs, below) runs wholly on the device -- pixel stage and
+entropy coder -- and is byte-identical to PIL's Image.save(format="JPEG", quality, subsampling).
 """
 import ctypes
 
@@ -92,3 +95,100 @@ def decode(data, device, bgr=False, pin=True):
 def read_file(path, device, bgr=False):
     with open(path, "rb") as f:
         return decode(f.read(), device, bgr=bgr)
+
+
+# ------------------------------------------------------------------------------------------ encode
+# Byte-identical to PIL's Image.save(format="JPEG", quality=q, subsampling=s) (libjpeg-turbo, the
+# encoder behind cv2.imwrite too): the pixel stage (colour, chroma downsampling, islow forward DCT,
+# quantisation: mx_jpeg_forward) and the entropy coder (mx_jpeg_entropy) both run on the device; only
+# the finished scan bytes come back.
+_EOI = b"\xff\xd9"
+
+
+def _rc(rc):
+    if rc == -2:
+        raise JpegUnsupported(_lib.load().mx_last_error().decode())
+    if rc != 0:
+        raise ValueError(_lib.load().mx_last_error().decode())
+
+
+def encode_info(width, height, quality=95, subsampling=2):
+    """JpegInfo of an encode: geometry, scaled Annex K quantisation tables, standard Huffman tables.
+    subsampling in PIL's numbering: 0 = 4:4:4, 2 = 4:2:0."""
+    info = JpegInfo()
+    _rc(_lib.load().mx_jpeg_encode_info(int(width), int(height), int(quality), int(subsampling), ctypes.byref(info)))
+    return info
+
+
+def header(info):
+    """The marker segments from SOI up to and including SOS (host)."""
+    buf = np.empty(2048, dtype=np.uint8)
+    n = ctypes.c_int64(0)
+    _rc(_lib.load().mx_jpeg_write_header(ctypes.byref(info), buf.ctypes.data, buf.size, ctypes.byref(n)))
+    return buf[:n.value].tobytes()
+
+
+def encode_coefs(info, coefs):
+    """Host Huffman coder: quantised natural-order int16 coefficients (decode_coefs' layout; a numpy
+    array or a CPU tensor) with the tables of `info` -> the complete JPEG file as bytes."""
+    if torch.is_tensor(coefs):
+        coefs = coefs.numpy()
+    coefs = np.ascontiguousarray(coefs, dtype=np.int16).reshape(-1)
+    if coefs.size < info.coef_total:
+        raise ValueError("encode_coefs: fewer than coef_total coefficients")
+    lib = _lib.load()
+    head = header(info)
+    buf = np.empty(max(int(lib.mx_jpeg_scan_bound(ctypes.byref(info))), 1), dtype=np.uint8)
+    n = ctypes.c_int64(0)
+    _rc(lib.mx_jpeg_encode_coefs(ctypes.byref(info), coefs.ctypes.data, buf.ctypes.data, buf.size, ctypes.byref(n)))
+    return head + buf[:n.value].tobytes() + _EOI
+
+
+def forward(img, info, bgr=False):
+    """Device pixel stage: uint8 [H, W, 3] device tensor -> int16 [coef_total] device tensor of the
+    quantised coefficients libjpeg-turbo would code (dummy blocks included)."""
+    coefs = torch.empty(info.coef_total, dtype=torch.int16, device=img.device)
+    _lib.call("mx_jpeg_forward", img.data_ptr(), int(bool(bgr)), ctypes.byref(info), coefs.data_ptr(), _lib.stream())
+    return coefs
+
+
+def encode(img, quality=95, subsampling=2, bgr=False, entropy="device"):
+    """uint8 [H, W, 3] device tensor (RGB, or BGR with bgr=True) -> the bytes of the JPEG file PIL's
+    Image.save(format="JPEG", quality=quality, subsampling=subsampling) writes for those pixels.
+    entropy="device": the Huffman coder runs on the device too (mx_jpeg_entropy) and two host
+    synchronisations happen per image: reading the length of the scan (one int64), then copying that
+    many bytes back. entropy="host": the coefficients are copied back (one synchronisation) and coded
+    by mx_jpeg_encode_coefs. Grey, 4:2:2 and non-uint8 input raise ValueError."""
+    if not (torch.is_tensor(img) and img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3):
+        raise ValueError("encode: a uint8 [H, W, 3] tensor is required")
+    if img.device.type != "cuda":
+        raise ValueError("encode: a device tensor is required")
+    if subsampling not in (0, 2):
+        raise ValueError("encode: subsampling 0 (4:4:4) or 2 (4:2:0) only")
+    if entropy not in ("device", "host"):
+        raise ValueError("encode: entropy is 'device' or 'host'")
+    img = img.contiguous()
+    info = encode_info(img.shape[1], img.shape[0], quality, subsampling)
+    with torch.cuda.device(img.device):
+        coefs = forward(img, info, bgr)
+        if entropy == "host":
+            return encode_coefs(info, coefs.cpu())
+        lib = _lib.load()
+        ws = torch.empty(lib.mx_jpeg_entropy_workspace(ctypes.byref(info)), dtype=torch.uint8, device=img.device)
+        cap = int(lib.mx_jpeg_scan_bound(ctypes.byref(info)))
+        out = torch.empty(cap, dtype=torch.uint8, device=img.device)
+        nbytes = torch.empty(1, dtype=torch.int64, device=img.device)
+        _lib.call("mx_jpeg_entropy", coefs.data_ptr(), ctypes.byref(info), ws.data_ptr(), ws.numel(), out.data_ptr(),
+                  cap, nbytes.data_ptr(), _lib.stream())
+        n = int(nbytes.item())  # synchronisation 1
+        if n < 0 or n > cap:
+            raise _lib.MxError(f"mx_jpeg_entropy: scan of {n} bytes (capacity {cap})")
+        scan = out[:n].cpu().numpy().tobytes()  # synchronisation 2
+    return header(info) + scan + _EOI
+
+
+def write_file(path, img, **kw):
+    """encode(img, **kw) written to `path`."""
+    data = encode(img, **kw)
+    with open(path, "wb") as f:
+        f.write(data)

@@ -10,9 +10,12 @@ work runs on the device (mx_det.augment: noise add/clip/truncate, cv2.filter2D m
 down + INTER_LINEAR up; bit-exact against the reference's apply_noise golden and the OpenCV
 restatements in oracle/). Each source JPEG is decoded on the device (mx_det.jpeg: host entropy decode,
 device IDCT / upsampling / colour, bit-identical to cv2.imread's libjpeg-turbo decode, in BGR like
-cv2.imread; PIL decodes the formats it does not handle), corrupted there, and copied back once for the
-JPEG encode (PIL / libjpeg-turbo, cv2.imwrite's default quality 95).
+cv2.imread; PIL decodes the formats it does not handle), corrupted there, and encoded there
+(mx_det.jpeg.encode: byte-identical to PIL / libjpeg-turbo at cv2.imwrite's default quality 95), so
+only the bytes of the written file come back. MX_JPEG_ENCODE=host copies the pixels back and lets PIL
+encode them instead.
 """
+import os
 import shutil
 from pathlib import Path
 
@@ -82,6 +85,12 @@ def _read_bgr(path):
 
 
 def _write_bgr(path, img_bgr):
+    """cv2.imwrite(path, img) at its default quality 95. A device tensor is encoded on the device
+    (mx_det.jpeg.encode: the same bytes as PIL / libjpeg-turbo) and only the file's bytes come back;
+    numpy input, or MX_JPEG_ENCODE=host, takes the PIL encode."""
+    if torch.is_tensor(img_bgr) and img_bgr.is_cuda and os.environ.get("MX_JPEG_ENCODE", "device") != "host":
+        jpeg.write_file(path, img_bgr, quality=95, bgr=True)
+        return
     if torch.is_tensor(img_bgr):
         img_bgr = img_bgr.cpu().numpy()
     Image.fromarray(np.ascontiguousarray(img_bgr[..., ::-1])).save(path, quality=95)

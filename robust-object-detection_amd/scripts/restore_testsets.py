@@ -1,9 +1,12 @@
 """Write U-Net-restored copies of the corrupted COCO test sets — `python -m scripts.restore_testsets`.
 
 Reference restore_testsets.py:82-159: Noise / Blur / LowRes images restored, annotations copied, Clean
-copied unchanged; JPEG output. Here the restoration itself runs on the GPU (mx_det.unet.restore_u8);
-decode/encode stay on the host (PIL). The fused eval path (eval_restored.py) skips this step.
+copied unchanged; JPEG output. Here the restoration runs on the GPU (mx_det.unet.restore_u8), and so
+do the JPEG decode (mx_det.jpeg.read_file; PIL for the files it does not handle) and the quality-95
+encode (mx_det.jpeg.write_file), both bit-identical to libjpeg-turbo: pixels never visit the host.
+MX_JPEG_ENCODE=host encodes with PIL instead. The fused eval path (eval_restored.py) skips this step.
 """
+import os
 import shutil
 from pathlib import Path
 
@@ -12,11 +15,29 @@ import torch
 from PIL import Image
 
 from scripts import eval_restored
+from mx_det import jpeg
 from mx_det.engine import init_device
 
 COCO_TESTSET_ROOT = Path("data/testsets/coco6")
 COCO_OUT_ROOT = Path("data/testsets/coco6_restored")
 VARIANTS_TO_RESTORE = ["Test_Noise", "Test_Blur", "Test_LowRes"]
+
+
+def read_rgb(path, dev):
+    """Image.open(path).convert("RGB") as a uint8 [H, W, 3] tensor on `dev`."""
+    try:
+        return jpeg.read_file(path, dev)
+    except (jpeg.JpegUnsupported, ValueError):
+        with Image.open(path) as im:
+            return torch.from_numpy(np.asarray(im.convert("RGB"), dtype=np.uint8).copy()).to(dev)
+
+
+def write_rgb(path, img):
+    """Image.fromarray(img).save(path, quality=95) of a uint8 [H, W, 3] device tensor."""
+    if os.environ.get("MX_JPEG_ENCODE", "device") == "host":
+        Image.fromarray(img.cpu().numpy()).save(path, quality=95)
+    else:
+        jpeg.write_file(path, img, quality=95)
 
 
 def restore_variant(unet, variant, dev, src_root=None, dst_root=None):
@@ -30,9 +51,7 @@ def restore_variant(unet, variant, dev, src_root=None, dst_root=None):
         shutil.copy2(f, dst_ann / f.name)
     files = sorted(src_img.glob("*.jpg"))
     for i, p in enumerate(files):
-        img = torch.from_numpy(np.asarray(Image.open(p).convert("RGB"), dtype=np.uint8).copy()).to(dev)
-        out = unet.restore_u8(img[None])[0].cpu().numpy()
-        Image.fromarray(out).save(dst_img / p.name, quality=95)
+        write_rgb(dst_img / p.name, unet.restore_u8(read_rgb(p, dev)[None])[0])
         if (i + 1) % 100 == 0 or i + 1 == len(files):
             print(f"    COCO {variant}: {i + 1}/{len(files)}", flush=True)
 
