@@ -976,7 +976,7 @@ def conv_bn_act_maxpool(x, conv, bn, act, k, st, pd):
     (mx_bn_act_maxpool), so the full-resolution activation is written once (the conv output) and
     never re-written. Same running-stat update and result as conv_bn + maxpool."""
     assert is_x3(x) and bn.training
-    if bn.num_batches_tracked is not None and id(bn) not in _nbt_batched:
+    if bn.num_batches_tracked is not None and not batch_counted(bn):
         bn.num_batches_tracked.add_(1)
     w = conv.weight
     wk, _ = operands(w, x.shape[3], conv.stride, conv.padding, _ceil8(w.shape[0]), False, split=True)
@@ -1105,17 +1105,27 @@ class BatchNorm2d(torch.nn.Module):
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
 
 
-_nbt_batched = set()
+_nbt_token = object()
 
 
 def count_batches(bns):
     """num_batches_tracked += 1 for every module in `bns` in one foreach launch (called once per
-    training forward by the model); conv_bn then skips its own per-layer increment for them."""
-    global _nbt_batched
+    training forward by the model); conv_bn then skips its own per-layer increment for them
+    (batch_counted). The modules themselves carry the mark, the token of this call: a set of id()s
+    outlived its modules, and a module allocated later at a freed one's address -- another model
+    built once the first was dropped -- then never counted its batches."""
+    global _nbt_token
     t = [b.num_batches_tracked for b in bns if b.num_batches_tracked is not None]
     if t:
         torch._foreach_add_(t, 1)
-    _nbt_batched = {id(b) for b in bns}
+    _nbt_token = tok = object()
+    for b in bns:
+        b.__dict__["_mx_nbt"] = tok
+
+
+def batch_counted(bn):
+    """True if the latest count_batches call already counted this forward for `bn`."""
+    return bn.__dict__.get("_mx_nbt") is _nbt_token
 
 
 class ResLink:
@@ -1148,7 +1158,7 @@ def conv_bn(x, conv, bn, act, residual=None, link=None, bnb_own=None, bnb_feed=N
     """Conv2d(bias=False) + BatchNorm2d (+ residual) + activation as one fused unit. Train mode:
     batch statistics + running-stat update (nn.BatchNorm2d semantics); eval: BN folded into the conv."""
     if bn.training:
-        if bn.num_batches_tracked is not None and id(bn) not in _nbt_batched:
+        if bn.num_batches_tracked is not None and not batch_counted(bn):
             bn.num_batches_tracked.add_(1)
         return ConvBNAct.apply(x, conv.weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
                                conv.stride, conv.padding, act, bn.eps, bn.momentum, link, bnb_own, bnb_feed)

@@ -114,3 +114,25 @@ def test_rpn_canvas_layout_frames_levels():
     for (h, w), (y, x) in zip(hws, pos):
         inner[y + 1:y + h + 1, x + 1:x + w + 1] += 1
     assert int((inner * (occ - 1)).sum()) == 0  # no level pixel lies in another level's frame
+
+
+def test_batch_count_mark_does_not_outlive_its_modules():
+    """conv.count_batches marks the BatchNorm modules it counted, and conv_bn skips its own increment
+    only for those (conv.batch_counted). The mark must die with the modules: kept as a set of id()s it
+    made a module allocated later at a freed one's address -- the next model built in the process --
+    look counted, and its num_batches_tracked stayed 0."""
+    from mx_det import conv as mc
+    bns = [mc.BatchNorm2d(8) for _ in range(64)]
+    mc.count_batches(bns)
+    assert all(int(b.num_batches_tracked) == 1 and mc.batch_counted(b) for b in bns)
+    other = mc.BatchNorm2d(8)
+    assert not mc.batch_counted(other)
+    mc.count_batches([other])  # the latest call alone holds
+    assert mc.batch_counted(other) and not any(mc.batch_counted(b) for b in bns)
+    mc.count_batches(bns)
+    stale = {id(b) for b in bns}
+    del bns
+    fresh = [mc.BatchNorm2d(8) for _ in range(256)]  # CPython hands the freed addresses out again
+    assert not any(mc.batch_counted(b) for b in fresh), sum(id(b) in stale for b in fresh)
+    mc.count_batches([])  # an eval forward: nothing is counted
+    assert not mc.batch_counted(other)
