@@ -645,6 +645,51 @@ size_t mx_jpeg_entropy_workspace(const mx_jpeg_info* info);
 int mx_jpeg_entropy(const int16_t* coefs_dev, const mx_jpeg_info* info, void* ws, size_t ws_bytes, uint8_t* out_dev,
                     int64_t out_cap, int64_t* nbytes_dev, mx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCOeval (bbox) on the device: pycocotools' COCOeval.evaluate (computeIoU + evaluateImg) and
+ * accumulate, as train_frcnn_baseline.py:92-96 and eval_all.py:131-156 call them. f64 throughout, every
+ * operation rounded once and in the host code's order (maskApi bbIou; mx_det/coco.py is the restated
+ * host form): the outputs are bit-identical to it.
+ *   Layout. A segment is one (image, category) pair with at least one GT or one detection; the S
+ *   segments are ordered by (category index, image index). Detections [ND] are sorted by (category,
+ *   image, score descending, ties in result order) and each segment holds at most maxDets[-1] of them;
+ *   GT [NG] by (category, image, annotation order). dt_off / gt_off [S+1] int32 are the segments'
+ *   offsets into them. dt_xywh [ND][4], dt_area [ND] (w*h); gt_xywh [NG][4], gt_area [NG] (the
+ *   annotation's area field), gt_crowd [NG] u8, gt_id [NG]. area_rng [A][2], iou_thr [T], rec_thr [R]
+ *   (ascending) f64 and max_dets [M] int32 are device arrays holding the host's parameter values.
+ *   max_g / max_d: upper bounds on one segment's GT / detection count (NG / ND are always safe).
+ *   mx_coco_match   one launch, one wave per (segment, area range, threshold): a GT is ignored when
+ *                   crowd or its area is outside [a0, a1]; detections in score order take the
+ *                   still-free GT (crowd GTs stay free) of highest IoU >= min(t, 1 - 1e-10), non-ignored
+ *                   GTs before ignored ones, the later annotation among equal IoUs.
+ *                   dtm [A][T][ND] = the matched GT's id (0: none), dt_ig [A][T][ND] u8 = the matched
+ *                   GT's ignore flag, or 1 when dtm == 0 and the detection's area is outside the range,
+ *                   gt_ig [A][NG] u8. A 0/0 IoU never matches. MX_EUNSUPPORTED for max_g > 61440 (one
+ *                   flag byte per GT of a segment in LDS); a segment found above max_g on the device
+ *                   gets dtm = -1 rather than a truncated match.
+ *   mx_coco_accumulate  two launches. perm [ND] int64: for each category's range cat_dt_off[k] ..
+ *                   cat_dt_off[k+1] of the detections, their indices by score descending (stable);
+ *                   dt_score [ND]; cat_gt_off [K+1] the categories' GT ranges. For each (k, a, m, t) over
+ *                   the detections of rank < max_dets[m] in their segment: tp = dtm != 0 && !dt_ig,
+ *                   fp = dtm == 0 && !dt_ig, running sums, recall tp / npig, precision
+ *                   tp / (fp + tp + 2^-52) made non-increasing from the right, sampled with its score
+ *                   at searchsorted(recall, rec_thr, left) (0 past the last detection).
+ *                   precision / scores [T][R][K][A][M], recall [T][K][A][M]; every entry is written,
+ *                   -1 where the category has no non-ignored GT. R <= 2048. Workspace
+ *                   mx_coco_accumulate_workspace(ND).
+ * ------------------------------------------------------------------------------------------- */
+int mx_coco_match(const double* dt_xywh, const double* dt_area, const int32_t* dt_off, int64_t ND,
+                  const double* gt_xywh, const double* gt_area, const uint8_t* gt_crowd, const int64_t* gt_id,
+                  const int32_t* gt_off, int64_t NG, int64_t S, const double* area_rng, int64_t A,
+                  const double* iou_thr, int64_t T, int64_t max_g, int64_t max_d, int64_t* dtm, uint8_t* dt_ig,
+                  uint8_t* gt_ig, mx_stream_t stream);
+size_t mx_coco_accumulate_workspace(int64_t ND);
+int mx_coco_accumulate(const int64_t* dtm, const uint8_t* dt_ig, const uint8_t* gt_ig, const double* dt_score,
+                       const int64_t* perm, const int32_t* dt_off, int64_t S, int64_t ND, int64_t NG,
+                       const int32_t* cat_dt_off, const int32_t* cat_gt_off, int64_t K, int64_t A, int64_t T,
+                       const int32_t* max_dets, int64_t M, const double* rec_thr, int64_t R, double* precision,
+                       double* scores, double* recall, void* ws, size_t ws_bytes, mx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,11 @@ _SIGS = {
                                    c_vp, c_i64, c_vp, c_sz, c_vp]),
     "mx_conv2d_wgrad_x3": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_sz,
                                    c_vp]),
+    "mx_coco_match": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
+                              c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mx_coco_accumulate_workspace": (c_sz, [c_i64]),
+    "mx_coco_accumulate": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64,
+                                   c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

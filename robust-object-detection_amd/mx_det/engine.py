@@ -7,7 +7,8 @@ Behaviour follows the reference entry points:
     elapsed_sec}; last.pth {"model", "epoch"} every epoch; final COCOeval on the val split; best.pth
     {"model", "epoch": "final", "metrics"}; a final history record with epoch "final".
   eval: scripts/eval_all.py:97-156 — bs=1 inference, xyxy -> xywh result dicts, COCOeval bbox,
-    stats[0]/[1], per-class AP50 from precision[0, :, k, 0, 2].
+    stats[0]/[1], per-class AP50 from precision[0, :, k, 0, 2]. MX_DEVICE_COCOEVAL=1 keeps the
+    detections on the device and runs COCOeval there (mx_det.coco_device), same numbers bit for bit.
 MI355X-side differences: images stay uint8 until the device (ToImage/ToDtype scaling, corruption and
 normalisation run as HIP kernels); with WORLD_SIZE > 1 (torchrun) every rank trains on its shard of
 each epoch's permutation (DistributedSampler, drop_last: no padded duplicates in the loss sum) with
@@ -108,9 +109,75 @@ def _append_jsonl(path, rec):
         f.write(json.dumps(rec, ensure_ascii=False) + "\n")
 
 
+def _eval_metrics(ev, gt, per_class):
+    out = {"mAP50_95": float(ev.stats[0]), "mAP50": float(ev.stats[1])}
+    if per_class:
+        prec = ev.eval["precision"]
+        pc = {}
+        for k, cat_id in enumerate(gt.getCatIds()):
+            name = gt.loadCats(cat_id)[0]["name"]
+            ap = prec[0, :, k, 0, 2]
+            ap = ap[ap > -1]
+            pc[name] = float(np.mean(ap)) if len(ap) else 0.0
+        out["per_class_ap50"] = pc
+    return out
+
+
+def _evaluate_device(model, loader, ann_file, dev, per_class):
+    """evaluate() with the detections kept on the device and COCOeval run there (mx_det.coco_device):
+    per image one packed [n, 7] f64 block (image id, xyxy, score, label; every field exact in f64), no
+    host copy of the outputs; with world > 1 the ranks' packed arrays are combined by one collective
+    and rank 0 evaluates."""
+    from .coco_device import DeviceCOCOeval
+    world, rank, _ = dist_info()
+    COCO, _ = get_coco_api()
+    model.eval()
+    parts = []
+    for images, targets in loader:
+        imgs = [im.to(dev, non_blocking=True) for im in images]
+        outs = model(imgs)
+        for out, tgt in zip(outs, targets):
+            n = out["boxes"].shape[0]
+            img_id = tgt["image_id"].to(dev, torch.float64, non_blocking=True).reshape(1, 1).expand(n, 1)
+            parts.append(torch.cat([img_id, out["boxes"].float().double().reshape(n, 4),
+                                    out["scores"].float().double().reshape(n, 1),
+                                    out["labels"].double().reshape(n, 1)], 1))
+    packed = torch.cat(parts) if parts else torch.empty((0, 7), dtype=torch.float64, device=dev)
+    if world > 1:
+        # rank-major concatenation (the host path's order) as a sum of disjoint slices: the f64 rows
+        # travel as their int64 bit patterns (x + 0 is exact for every bit pattern), and all_reduce
+        # takes device tensors over RCCL and over gloo alike
+        counts = torch.zeros(world, dtype=torch.int64, device=dev)
+        counts[rank] = packed.shape[0]
+        dist.all_reduce(counts)
+        counts = counts.tolist()
+        allp = torch.zeros((sum(counts), 7), dtype=torch.int64, device=dev)
+        start = sum(counts[:rank])
+        allp[start:start + counts[rank]] = packed.view(torch.int64)
+        if allp.numel():
+            dist.all_reduce(allp)
+        packed = allp.view(torch.float64)
+    if rank != 0:
+        return None
+    if packed.shape[0] == 0:
+        return {"mAP50_95": 0.0, "mAP50": 0.0, **({"per_class_ap50": {}} if per_class else {})}
+    gt = COCO(ann_file)
+    ev = DeviceCOCOeval(gt, dev)
+    ev.add(packed[:, 0].long(), packed[:, 1:5].float(), packed[:, 5].float(), packed[:, 6].long())
+    ev.evaluate()
+    ev.accumulate()
+    ev.summarize()
+    return _eval_metrics(ev, gt, per_class)
+
+
 @torch.no_grad()
-def evaluate(model, loader, ann_file, dev, per_class=False):
-    """COCOeval of a model over a loader of (uint8 HWC image, target) with bs=1."""
+def evaluate(model, loader, ann_file, dev, per_class=False, device_eval=None):
+    """COCOeval of a model over a loader of (uint8 HWC image, target) with bs=1. device_eval: run
+    COCOeval on the device (None: env MX_DEVICE_COCOEVAL, default "0" = the host evaluator)."""
+    if device_eval is None:
+        device_eval = os.environ.get("MX_DEVICE_COCOEVAL", "0") != "0"
+    if device_eval:
+        return _evaluate_device(model, loader, ann_file, dev, per_class)
     world, rank, _ = dist_info()
     COCO, COCOeval = get_coco_api()
     model.eval()
@@ -139,17 +206,7 @@ def evaluate(model, loader, ann_file, dev, per_class=False):
     ev.evaluate()
     ev.accumulate()
     ev.summarize()
-    out = {"mAP50_95": float(ev.stats[0]), "mAP50": float(ev.stats[1])}
-    if per_class:
-        prec = ev.eval["precision"]
-        pc = {}
-        for k, cat_id in enumerate(gt.getCatIds()):
-            name = gt.loadCats(cat_id)[0]["name"]
-            ap = prec[0, :, k, 0, 2]
-            ap = ap[ap > -1]
-            pc[name] = float(np.mean(ap)) if len(ap) else 0.0
-        out["per_class_ap50"] = pc
-    return out
+    return _eval_metrics(ev, gt, per_class)
 
 
 def train_frcnn(cfg):
