@@ -605,6 +605,53 @@ int mx_jpeg_reconstruct(const int16_t* coefs, const mx_jpeg_info* info, void* ws
                         int bgr, mx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Entropy decoding on the device: the scan of a file mx_jpeg_parse accepts (1 or 3 components, any
+ * accepted sampling, custom Huffman tables, restart intervals) -> the coefficients
+ * mx_jpeg_decode_coefs produces, bit for bit, whenever the status word is 0. A Huffman stream
+ * re-synchronises: a decoder started at a wrong bit falls into step with the true one after a few
+ * symbols, so lanes decode fixed-size subsequences speculatively and a fix-up iteration makes every
+ * lane's start state the true one (the exact sequential result, not an approximation).
+ *   mx_jpeg_entropy_decode  device: scan_dev = the file's bytes from info->scan_off to its end
+ *                         (nbytes of them, in HBM, any byte alignment) -> coefs_dev, int16
+ *                         [comp][by][bx][64] natural order (coef_total of them, ready for
+ *                         mx_jpeg_reconstruct) and *status_dev (one int32: 0, or MX_JPEG_ST_* bits).
+ *                         Passes: (1) markers and FF 00 pairs per 4-KiB chunk, scans, compaction to the
+ *                         unstuffed stream + restart-segment starts; (2) one lane per subsequence of
+ *                         S bits walks from an assumed state and records its exit state; (3) lanes
+ *                         re-walk from their predecessor's exit state to a fixed point: inside a
+ *                         workgroup with barriers, across workgroups by further launches that exit at
+ *                         once when the launch before changed no workgroup's last exit state (at most
+ *                         workgroups - 1 of them; no workgroup waits on another); (4) scan of the blocks
+ *                         completed per lane; (5) the output is cleared and every lane walks from its
+ *                         true state storing AC values and DC differences; (6) per-component DC prefix
+ *                         sums in 32 bits, reset at restart segments. No host synchronisation.
+ *                         With a non-zero status the coefficients are unspecified (callers decode
+ *                         that file with mx_jpeg_decode_coefs, which also defines what a damaged stream
+ *                         decodes to). MX_EINVAL before any HIP call for null pointers, nbytes <= 0 or
+ *                         >= 2^31, a short or misaligned (256 B) workspace, coefs_dev not 16-byte
+ *                         aligned, a Huffman table the host decoder rejects.
+ *   mx_jpeg_entropy_decode_workspace  bytes of ws for a scan of nbytes (0 for a bad info / nbytes).
+ *   mx_jpeg_entropy_decode_set_subseq  S in bits: 64 (minimum) .. 65536, default 512; MX_EINVAL
+ *                         outside. A process setting, results identical (tests run at the minimum,
+ *                         where a 64x64 image has as many lanes as a 1333x800 one at the default).
+ *   mx_jpeg_decode_coefs_chunked  host: the same passes run serially over the whole file `data`
+ *                         (workgroups of 256 lanes emulated), sharing the per-symbol walk with the
+ *                         kernels (csrc/mx_jpeg_walk.h). The CPU reference of the kernels, not a
+ *                         product path. subseq_bits 0: the current setting.
+ * ------------------------------------------------------------------------------------------- */
+#define MX_JPEG_ST_CODE 1     /* a bit pattern that is no Huffman code */
+#define MX_JPEG_ST_DC 2       /* DC size over 11 */
+#define MX_JPEG_ST_RUN 4      /* AC run past coefficient 63 */
+#define MX_JPEG_ST_SHORT 8    /* data exhausted or a marker reached before a segment's last MCU */
+#define MX_JPEG_ST_RESTART 16 /* the number of restart markers does not fit the restart interval */
+size_t mx_jpeg_entropy_decode_workspace(const mx_jpeg_info* info, int64_t nbytes);
+int mx_jpeg_entropy_decode(const uint8_t* scan_dev, int64_t nbytes, const mx_jpeg_info* info, void* ws, size_t ws_bytes,
+                           int16_t* coefs_dev, int32_t* status_dev, mx_stream_t stream);
+int mx_jpeg_entropy_decode_set_subseq(int bits);
+int mx_jpeg_decode_coefs_chunked(const uint8_t* data, int64_t n, const mx_jpeg_info* info, int subseq_bits,
+                                 int16_t* coefs_host, int32_t* status);
+
+/* ---------------------------------------------------------------------------------------------
  * Baseline JPEG encode (replaces the PIL / cv2.imwrite JPEG encode of build_corrupted_testsets.py
  * and restore_testsets.py). Byte-identical to libjpeg-turbo behind PIL's
  * Image.save(format="JPEG", quality=q, subsampling=s): SOI, JFIF APP0, two DQT, SOF0, four DHT (the

@@ -11,7 +11,10 @@
 // per_scan_setup) for the coefficient layout.
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/mx_det.h"
+#include "mx_jpeg_walk.h"
 
 namespace mx {
 void set_error(const char* fmt, ...);
@@ -40,6 +43,7 @@ struct Huff {
 };
 
 bool huff_counts_ok(const uint8_t* bits);
+const char* enc_check(const mx_jpeg_info* info);  // below: geometry the coders rely on
 
 bool build_huff(const uint8_t* bits, const uint8_t* vals, Huff* h) {
   if (!huff_counts_ok(bits)) return false;
@@ -359,6 +363,179 @@ extern "C" int mx_jpeg_decode_coefs(const uint8_t* d, int64_t n, const mx_jpeg_i
     }
     if (ri) --left;
   }
+  return MX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Parallel entropy decode, host half: the tables and geometry mx_jpeg_entropy_decode (mx_jpeg.hip)
+// uploads, and mx_jpeg_decode_coefs_chunked, the serial restatement of its passes (unstuff,
+// speculative walks, synchronisation to a fixed point, scan, write, DC sums) over the walk both
+// share (mx_jpeg_walk.h).
+// ------------------------------------------------------------------------------------------------
+namespace {
+int g_jd_subseq = mx::kJdSubseqDefault;
+}
+
+namespace mx {
+
+int jpeg_dec_subseq() { return g_jd_subseq; }
+
+bool jpeg_dec_tables(const mx_jpeg_info* info, JdHuff* tabs) {
+  memset(tabs, 0, sizeof(JdHuff) * kJdTables);
+  for (int c = 0; c < info->ncomp; ++c)
+    for (int ac = 0; ac < 2; ++ac) {
+      const int t = ac ? 4 + info->ta[c] : info->td[c];
+      Huff h;
+      if (info->td[c] > 3 || info->ta[c] > 3 || !build_huff(info->hbits[t], info->hval[t], &h)) return false;
+      JdHuff& o = tabs[2 * c + ac];
+      memcpy(o.maxcode, h.maxcode, sizeof(o.maxcode));
+      o.valoff[0] = 0;
+      for (int l = 1; l <= 16; ++l) o.valoff[l] = h.valoff[l];
+      memcpy(o.val, h.val, sizeof(o.val));
+      for (int i = 0; i < 512; ++i) o.look[i] = (uint16_t)(h.look_len[i] ? (h.look_len[i] << 8) | h.look_val[i] : 0);
+    }
+  return true;
+}
+
+const char* jpeg_dec_geom(const mx_jpeg_info* info, int subseq, JdGeom* g) {
+  if (const char* e = enc_check(info)) return e;
+  if (info->restart_interval < 0) return "negative restart interval";
+  memset(g, 0, sizeof(*g));
+  g->ncomp = info->ncomp;
+  g->mcux = info->mcux;
+  for (int c = 0; c < 3; ++c) {
+    const bool on = c < info->ncomp;
+    g->h[c] = on ? info->h[c] : 1;
+    g->v[c] = on ? info->v[c] : 1;
+    g->bw[c] = on ? info->bw[c] : 0;
+    g->coef_off[c] = on ? info->coef_off[c] : 0;
+    g->first[c] = g->bpm;
+    if (on) g->bpm += info->h[c] * info->v[c];
+  }
+  const int64_t nmcu = (int64_t)info->mcux * info->mcuy;
+  g->nblk = nmcu * g->bpm;
+  if (g->nblk * 64 != info->coef_total) return "inconsistent coefficient total";
+  const int64_t ri = info->restart_interval;
+  g->segblk = ri ? ri * g->bpm : g->nblk;
+  g->nseg = ri ? (int32_t)((nmcu + ri - 1) / ri) : 1;
+  g->subseq = subseq;
+  return nullptr;
+}
+
+}  // namespace mx
+
+extern "C" int mx_jpeg_entropy_decode_set_subseq(int bits) {
+  if (bits < mx::kJdSubseqMin || bits > mx::kJdSubseqMax) {
+    mx::set_error("mx_jpeg_entropy_decode_set_subseq: %d .. %d bits", mx::kJdSubseqMin, mx::kJdSubseqMax);
+    return MX_EINVAL;
+  }
+  g_jd_subseq = bits;
+  return MX_OK;
+}
+
+extern "C" int mx_jpeg_decode_coefs_chunked(const uint8_t* d, int64_t n, const mx_jpeg_info* info, int subseq_bits,
+                                            int16_t* coefs, int32_t* status) {
+  using namespace mx;
+  if (!d || !info || !coefs || !status || info->scan_off <= 0 || info->scan_off >= n)
+    return fail(MX_EINVAL, "jpeg_decode_coefs_chunked: bad arguments");
+  const int S = subseq_bits ? subseq_bits : g_jd_subseq;
+  if (S < kJdSubseqMin || S > kJdSubseqMax) return fail(MX_EINVAL, "jpeg_decode_coefs_chunked: subsequence size out of range");
+  JdGeom g;
+  if (const char* e = jpeg_dec_geom(info, S, &g)) return fail(MX_EINVAL, e);
+  std::vector<JdHuff> tabs(kJdTables);
+  if (!jpeg_dec_tables(info, tabs.data())) return fail(MX_EINVAL, "jpeg: bad Huffman table");
+  int st = 0;
+  // ---- 1. find and unstuff: the data of every restart segment up to its first marker
+  const uint8_t* s = d + info->scan_off;
+  const int64_t ns = n - info->scan_off;
+  std::vector<uint32_t> words((size_t)(ns + 16) / 4 + 1, 0);  // the clean stream, zero padded
+  uint8_t* clean = (uint8_t*)words.data();
+  std::vector<int64_t> seg_start((size_t)g.nseg + 1, 0);
+  int64_t nclean = 0, rst = 0;
+  bool live = true;
+  for (int64_t i = 0; i < ns; ++i) {
+    const int f = jd_classify(i > 0 ? s[i - 1] : -1, s[i], i + 1 < ns ? s[i + 1] : -1);
+    if (f & kJdMarker) {
+      live = (f & kJdRst) != 0;
+      if (live && ++rst < g.nseg) seg_start[rst] = nclean;
+    } else if (live && !(f & kJdDrop)) {
+      clean[nclean++] = s[i];
+    }
+  }
+  for (int64_t j = (rst < g.nseg - 1 ? rst : g.nseg - 1) + 1; j <= g.nseg; ++j) seg_start[j] = nclean;
+  if (rst != g.nseg - 1) st |= MX_JPEG_ST_RESTART;
+  // ---- subsequences of every segment
+  std::vector<int64_t> sub_base((size_t)g.nseg + 1, 0);
+  for (int j = 0; j < g.nseg; ++j) {
+    const int64_t bits = (seg_start[j + 1] - seg_start[j]) * 8;
+    if (bits == 0) st |= MX_JPEG_ST_SHORT;
+    sub_base[j + 1] = sub_base[j] + (bits + S - 1) / S;
+  }
+  const int64_t total = sub_base[g.nseg];
+  std::vector<uint32_t> ex((size_t)total), lastin((size_t)total, 0), cnt((size_t)total);
+  std::vector<JdLane> lane((size_t)total);
+  // ---- 2. speculative walk: every lane from the assumed state (block start, DC next) at its first bit
+  for (int64_t i = 0; i < total; ++i) {
+    lane[i] = jd_lane(g, seg_start.data(), sub_base.data(), i);
+    ex[i] = jd_walk(words.data(), tabs.data(), g, jd_unpack(0, lane[i].boundary), lane[i].limit, lane[i].end, &cnt[i]);
+  }
+  // ---- 3. synchronise: rounds inside a workgroup to its fixed point, passes across workgroups
+  const int64_t nwg = (total + kJdLanes - 1) / kJdLanes;
+  std::vector<uint32_t> next(kJdLanes);
+  for (int64_t pass = 0; pass < (nwg > 0 ? nwg : 1); ++pass) {
+    bool boundary_changed = false;
+    for (int64_t w = pass; w < nwg; ++w) {
+      const int64_t i0 = w * kJdLanes, cntw = total - i0 < kJdLanes ? total - i0 : kJdLanes;
+      const uint32_t ex_last = ex[i0 + cntw - 1];
+      const uint32_t head = pass == 0 || w == 0 ? lastin[i0] : ex[i0 - 1];
+      for (int round = 0; round <= kJdLanes; ++round) {
+        bool any = false;
+        for (int64_t t = 0; t < cntw; ++t) {  // all lanes read ...
+          const int64_t i = i0 + t;
+          next[t] = lane[i].q == 0 ? 0 : (t == 0 ? head : ex[i - 1]);
+        }
+        for (int64_t t = 0; t < cntw; ++t) {  // ... then the changed ones walk
+          const int64_t i = i0 + t;
+          if (next[t] == lastin[i]) continue;
+          any = true;
+          lastin[i] = next[t];
+          if (next[t] == kJdEnd) {
+            ex[i] = kJdEnd;
+            cnt[i] = 0;
+          } else {
+            ex[i] = jd_walk(words.data(), tabs.data(), g, jd_unpack(next[t], lane[i].boundary), lane[i].limit, lane[i].end,
+                            &cnt[i]);
+          }
+        }
+        if (!any) break;
+      }
+      if (cntw == kJdLanes && ex[i0 + cntw - 1] != ex_last) boundary_changed = true;
+    }
+    if (pass > 0 && !boundary_changed) break;
+  }
+  // ---- 4. count and place
+  std::vector<int64_t> P((size_t)total + 1, 0);
+  for (int64_t i = 0; i < total; ++i) P[i + 1] = P[i] + cnt[i];
+  // ---- 5. write: AC values and DC differences
+  memset(coefs, 0, sizeof(int16_t) * (size_t)info->coef_total);
+  for (int64_t i = 0; i < total; ++i) {
+    const JdLane& l = lane[i];
+    const uint32_t in = l.q == 0 ? 0 : ex[i - 1];
+    st |= jd_walk_store(words.data(), tabs.data(), g, jd_unpack(in, l.boundary), in == kJdEnd, l.limit, l.end,
+                        P[i] - P[sub_base[l.seg]], l.quota, l.seg_first, l.last, coefs);
+  }
+  // ---- 6. DC prediction: running sums per component in scan order, reset at restart segments
+  for (int c = 0; c < g.ncomp; ++c) {
+    const int64_t ne = (int64_t)g.bw[c] * info->bh[c];
+    JdSeg run{0, 0};
+    for (int64_t e = 0; e < ne; ++e) {
+      int reset;
+      int16_t* p = coefs + jd_dc_off(g, c, e, &reset);
+      run = jd_seg_combine(run, JdSeg{reset, (int32_t)*p});
+      *p = (int16_t)run.v;
+    }
+  }
+  *status = st;
   return MX_OK;
 }
 

@@ -13,6 +13,7 @@
 //                    ycc_rgb_convert (jdcolor.c tables, SCALEBITS 16), grey replicated to RGB.
 // Both are integer kernels (no float anywhere), HBM-bound streaming work.
 #include "mx_common.h"
+#include "mx_jpeg_walk.h"
 
 namespace mx {
 
@@ -903,6 +904,520 @@ extern "C" int mx_jpeg_entropy(const int16_t* coefs, const mx_jpeg_info* info, v
   jpeg_scan_ff_kernel<<<1, 1024, 0, st>>>(e.wg_ff, e.scal, e.wg_ffoff, nbytes);
   MX_LAUNCH_CHECK();
   jpeg_stuff_kernel<<<(unsigned)e.nchunk, 256, 0, st>>>(e.words, e.scal, e.wg_ffoff, out, out_cap);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+// ================================================================================================
+// Entropy decoder, device half (mx_jpeg_entropy_decode; the walk itself is mx_jpeg_walk.h, shared with
+// the serial host restatement mx_jpeg_decode_coefs_chunked in mx_jpeg.cpp). A Huffman stream
+// re-synchronises, so fixed-size subsequences are decoded speculatively and a fix-up iteration gives
+// every lane its true start state: the result is the sequential decoder's, bit for bit.
+//   jd_mark / jd_scan_chunks / jd_compact   markers and FF 00 pairs per 4-KiB chunk (16 B per lane, the
+//                         neighbours of a lane's bytes read across lane and chunk boundaries), scans,
+//                         compaction to the unstuffed stream + the restart segments' first bytes;
+//   jd_seg                subsequences per segment, scan;
+//   jd_sync (pass 0)      every lane walks its subsequence from the assumed state, then the workgroup
+//                         iterates with barriers: lane i + 1 re-walks from lane i's exit state until no
+//                         input changes;
+//   jd_sync (pass p > 0)  the same from the previous workgroup's last exit state; exits at once when
+//                         pass p - 1 changed no workgroup's last exit state (a device flag). After pass
+//                         p the first p + 1 workgroups are final. No workgroup waits on another;
+//   jd_place              scan of the blocks completed per lane;
+//   jd_write              every lane walks from its true state: AC values, DC differences, status bits;
+//   jd_dc<0> / jd_dc_carry / jd_dc<1>   per-component DC prefix sums (32-bit, reset at restart segments).
+// Integer only. Every launch is sized on the host from the worst case and exits on the device totals.
+// ================================================================================================
+namespace mx {
+
+int jpeg_dec_subseq();  // mx_jpeg.cpp: the process setting (mx_jpeg_entropy_decode_set_subseq)
+
+struct JdWs {
+  int64_t *scal;  // [0] clean bytes, [1] restart markers found, [2] subsequences
+  JdHuff* tabs;
+  uint32_t *chunk_last, *chunk_rst, *chunk_pre, *chunk_post, *chunk_live, *chunk_rstoff;
+  int64_t* chunk_off;
+  uint32_t* clean;
+  int64_t *seg_start, *sub_base, *P;
+  uint32_t *gexit, *glastin, *gcnt, *flags;
+  int32_t *tile_f, *tile_v, *carry;
+  int64_t nchunk, maxsubs, nwg, ntile[3], ntiles;
+  size_t bytes;
+};
+
+static JdWs jd_ws(const mx_jpeg_info* info, const JdGeom& g, int64_t nbytes, void* ws, size_t cap) {
+  JdWs e;
+  e.nchunk = cdiv(nbytes + 15, kJdChunk);  // chunks are cut at 16-B aligned addresses: up to 15 bytes of lead-in
+  e.maxsubs = nbytes * 8 / g.subseq + g.nseg + 1;
+  e.nwg = cdiv(e.maxsubs, kJdLanes);
+  e.ntiles = 0;
+  for (int c = 0; c < 3; ++c) {
+    e.ntile[c] = c < g.ncomp ? cdiv((int64_t)info->bw[c] * info->bh[c], 256) : 0;
+    e.ntiles += e.ntile[c];
+  }
+  Carver cv(ws, cap);
+  e.scal = cv.take<int64_t>(8);
+  e.tabs = cv.take<JdHuff>(kJdTables);
+  e.chunk_last = cv.take<uint32_t>(e.nchunk);
+  e.chunk_rst = cv.take<uint32_t>(e.nchunk);
+  e.chunk_pre = cv.take<uint32_t>(e.nchunk);
+  e.chunk_post = cv.take<uint32_t>(e.nchunk);
+  e.chunk_live = cv.take<uint32_t>(e.nchunk);
+  e.chunk_rstoff = cv.take<uint32_t>(e.nchunk);
+  e.chunk_off = cv.take<int64_t>(e.nchunk);
+  e.clean = cv.take<uint32_t>((nbytes + 16) / 4 + 1);  // + the word a peek reads past the last bit
+  e.seg_start = cv.take<int64_t>((int64_t)g.nseg + 1);
+  e.sub_base = cv.take<int64_t>((int64_t)g.nseg + 1);
+  e.P = cv.take<int64_t>(e.maxsubs + 1);
+  e.gexit = cv.take<uint32_t>(e.maxsubs);
+  e.glastin = cv.take<uint32_t>(e.maxsubs);
+  e.gcnt = cv.take<uint32_t>(e.maxsubs);
+  e.flags = cv.take<uint32_t>(e.nwg + 1);
+  e.tile_f = cv.take<int32_t>(e.ntiles);
+  e.tile_v = cv.take<int32_t>(e.ntiles);
+  e.carry = cv.take<int32_t>(e.ntiles);
+  e.bytes = align_up(cv.off);
+  return e;
+}
+
+// exclusive scan over the N lanes of a workgroup with an associative op (sh: N elements); *total = all
+template <int N, typename T, typename Op>
+__device__ __forceinline__ T block_excl_scan_op(T v, T identity, T* sh, T* total, Op op) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int o = 1; o < N; o <<= 1) {
+    const T a = t >= o ? sh[t - o] : identity;
+    __syncthreads();
+    sh[t] = op(a, sh[t]);
+    __syncthreads();
+  }
+  const T ex = t > 0 ? sh[t - 1] : identity;
+  *total = sh[N - 1];
+  __syncthreads();
+  return ex;
+}
+struct OpAdd64 {
+  __device__ __forceinline__ int64_t operator()(int64_t a, int64_t b) const { return a + b; }
+};
+struct OpMax32 {
+  __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
+};
+struct OpMax64 {
+  __device__ __forceinline__ int64_t operator()(int64_t a, int64_t b) const { return a > b ? a : b; }
+};
+
+// The 16 scan bytes of lane `lane` of chunk `chunk` with their classes. Chunks and lanes are cut at
+// 16-B aligned addresses (the scan starts `mis` bytes into the first group). cls[k] < 0: byte outside
+// the scan. Returns the scan index of byte 0 of the group.
+__device__ __forceinline__ int64_t jd_group(const uint8_t* scan, int64_t n, int mis, int64_t chunk, int lane,
+                                            uint8_t (&b)[16], int (&cls)[16]) {
+  const int64_t i0 = chunk * kJdChunk + (int64_t)lane * 16 - mis;
+  if (i0 >= 0 && i0 + 16 <= n) {
+    *(uint4*)b = *(const uint4*)(scan + i0);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) b[k] = (i0 + k >= 0 && i0 + k < n) ? scan[i0 + k] : 0;
+  }
+  const int prev = (i0 - 1 >= 0 && i0 - 1 < n) ? (int)scan[i0 - 1] : -1;
+  const int next = (i0 + 16 >= 0 && i0 + 16 < n) ? (int)scan[i0 + 16] : -1;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const int64_t i = i0 + k;
+    const int p = k > 0 ? (i - 1 >= 0 ? (int)b[k - 1] : -1) : prev;
+    const int x = k < 15 ? (i + 1 < n ? (int)b[k + 1] : -1) : next;
+    cls[k] = (i >= 0 && i < n) ? jd_classify(p, b[k], x) : -1;
+  }
+  return i0;
+}
+
+// last marker of the lane's bytes: (index in the chunk + 1) * 2 + (it is an RSTn), 0 for none
+__device__ __forceinline__ uint32_t jd_last_marker(const int (&cls)[16], int lane) {
+  uint32_t last = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k)
+    if (cls[k] >= 0 && (cls[k] & kJdMarker)) last = (uint32_t)(lane * 16 + k + 1) * 2 + ((cls[k] & kJdRst) ? 1 : 0);
+  return last;
+}
+
+// (1a) per chunk: its last marker, its RSTn count, the data bytes before its first marker (kept only if
+// the chunk starts inside live data) and the data bytes kept whatever came before
+__global__ void __launch_bounds__(256) jd_mark_kernel(const uint8_t* __restrict__ scan, int64_t n, int mis, JdWs e) {
+  __shared__ uint32_t sh[256];
+  __attribute__((aligned(16))) uint8_t b[16];
+  int cls[16];
+  jd_group(scan, n, mis, blockIdx.x, threadIdx.x, b, cls);
+  const uint32_t mine = jd_last_marker(cls, threadIdx.x);
+  uint32_t last;
+  const uint32_t before = block_excl_scan_op<256>(mine, 0u, sh, &last, OpMax32());
+  int state = before == 0 ? -1 : (int)(before & 1);  // -1: no marker yet in this chunk
+  uint32_t pre = 0, post = 0, rst = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (cls[k] < 0) continue;
+    if (cls[k] & kJdMarker) {
+      state = (cls[k] & kJdRst) ? 1 : 0;
+      rst += state;
+    } else if (!(cls[k] & kJdDrop)) {
+      pre += state < 0;
+      post += state > 0;
+    }
+  }
+  uint32_t tpre, tpost, trst;
+  block_excl_scan<256>(pre, sh, &tpre);
+  block_excl_scan<256>(post, sh, &tpost);
+  block_excl_scan<256>(rst, sh, &trst);
+  if (threadIdx.x == 0) {
+    e.chunk_last[blockIdx.x] = last;
+    e.chunk_pre[blockIdx.x] = tpre;
+    e.chunk_post[blockIdx.x] = tpost;
+    e.chunk_rst[blockIdx.x] = trst;
+  }
+}
+
+// (1b) one workgroup: whether each chunk starts in live data, its first clean byte, its first RSTn's
+// number; the totals; the starts of the segments no marker opens
+__global__ void __launch_bounds__(1024) jd_scan_chunks_kernel(JdWs e, int64_t nchunk, int nseg, int32_t* status) {
+  __shared__ int64_t sh[1024];
+  int64_t c_last = 0, c_off = 0, c_rst = 0;  // carries: last marker (chunk * 2^14 + in-chunk code), sums
+  for (int64_t base = 0; base < nchunk; base += 1024) {
+    const int64_t c = base + threadIdx.x;
+    const bool on = c < nchunk;
+    const uint32_t lm = on ? e.chunk_last[c] : 0;
+    int64_t tot;
+    int64_t before = block_excl_scan_op<1024>(lm ? (c << 14) + lm : (int64_t)0, (int64_t)0, sh, &tot, OpMax64());
+    before = before > c_last ? before : c_last;
+    c_last = tot > c_last ? tot : c_last;
+    const bool live = before == 0 || (before & 1);
+    const int64_t keep = on ? (int64_t)e.chunk_post[c] + (live ? e.chunk_pre[c] : 0) : 0;
+    const int64_t off = block_excl_scan_op<1024>(keep, (int64_t)0, sh, &tot, OpAdd64());
+    if (on) {
+      e.chunk_live[c] = live;
+      e.chunk_off[c] = c_off + off;
+    }
+    c_off += tot;
+    const int64_t ro = block_excl_scan_op<1024>(on ? (int64_t)e.chunk_rst[c] : 0, (int64_t)0, sh, &tot, OpAdd64());
+    if (on) e.chunk_rstoff[c] = (uint32_t)(c_rst + ro);
+    c_rst += tot;
+  }
+  if (threadIdx.x == 0) {
+    e.scal[0] = c_off;
+    e.scal[1] = c_rst;
+    e.seg_start[0] = 0;
+    if (c_rst != nseg - 1) atomicOr(status, MX_JPEG_ST_RESTART);
+  }
+  const int64_t first = (c_rst < nseg - 1 ? c_rst : nseg - 1) + 1;
+  for (int64_t j = first + threadIdx.x; j <= nseg; j += 1024) e.seg_start[j] = c_off;
+}
+
+// (1c) the clean stream and the segment starts
+__global__ void __launch_bounds__(256) jd_compact_kernel(const uint8_t* __restrict__ scan, int64_t n, int mis, JdWs e,
+                                                         int nseg) {
+  __shared__ uint32_t sh[256];
+  __attribute__((aligned(16))) uint8_t b[16];
+  int cls[16];
+  jd_group(scan, n, mis, blockIdx.x, threadIdx.x, b, cls);
+  const uint32_t mine = jd_last_marker(cls, threadIdx.x);
+  uint32_t last;
+  const uint32_t before = block_excl_scan_op<256>(mine, 0u, sh, &last, OpMax32());
+  const int state0 = before == 0 ? (int)e.chunk_live[blockIdx.x] : (int)(before & 1);
+  int state = state0;
+  uint32_t keep = 0, rst = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (cls[k] < 0) continue;
+    if (cls[k] & kJdMarker) {
+      state = (cls[k] & kJdRst) ? 1 : 0;
+      rst += state;
+    } else if (!(cls[k] & kJdDrop)) {
+      keep += state;
+    }
+  }
+  uint32_t tot;
+  const uint32_t kex = block_excl_scan<256>(keep, sh, &tot);
+  const uint32_t rex = block_excl_scan<256>(rst, sh, &tot);
+  int64_t pos = e.chunk_off[blockIdx.x] + kex;
+  int64_t r = (int64_t)e.chunk_rstoff[blockIdx.x] + rex;
+  const int64_t nclean = e.scal[0];
+  uint8_t* clean = (uint8_t*)e.clean;
+  state = state0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (cls[k] < 0) continue;
+    if (cls[k] & kJdMarker) {
+      state = (cls[k] & kJdRst) ? 1 : 0;
+      if (state) {
+        ++r;  // this marker opens segment r
+        if (r < nseg) e.seg_start[r] = pos;
+      }
+    } else if (!(cls[k] & kJdDrop) && state) {
+      if (pos < nclean) clean[pos] = b[k];
+      ++pos;
+    }
+  }
+}
+
+// (1d) one workgroup: subsequences of every segment, their scan; an empty segment is a short one
+__global__ void __launch_bounds__(1024) jd_seg_kernel(JdWs e, int nseg, int subseq, int32_t* status) {
+  __shared__ int64_t sh[1024];
+  int64_t carry = 0;
+  for (int64_t base = 0; base < nseg; base += 1024) {
+    const int64_t j = base + threadIdx.x;
+    int64_t ns = 0;
+    if (j < nseg) {
+      const int64_t bits = (e.seg_start[j + 1] - e.seg_start[j]) * 8;
+      if (bits <= 0) atomicOr(status, MX_JPEG_ST_SHORT);
+      ns = bits > 0 ? (bits + subseq - 1) / subseq : 0;
+    }
+    int64_t tot;
+    const int64_t ex = block_excl_scan_op<1024>(ns, (int64_t)0, sh, &tot, OpAdd64());
+    if (j < nseg) e.sub_base[j] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) {
+    e.sub_base[nseg] = carry;
+    e.scal[2] = carry;
+  }
+}
+
+__device__ __forceinline__ void jd_load_tabs(const JdHuff* tabs, uint32_t* sh) {
+  const uint32_t* src = (const uint32_t*)tabs;
+  for (int i = threadIdx.x; i < kJdHuffWords; i += blockDim.x) sh[i] = src[i];
+  __syncthreads();
+}
+
+// one component's two tables per launch: a kernel argument holds at most 4 KiB
+struct JdHuffPair {
+  JdHuff t[2];
+};
+__global__ void __launch_bounds__(256) jd_tables_kernel(JdHuffPair p, JdHuff* __restrict__ dst) {
+  const uint32_t* src = (const uint32_t*)&p;
+  uint32_t* d = (uint32_t*)dst;
+  for (int i = threadIdx.x; i < (int)(sizeof(JdHuffPair) / 4); i += 256) d[i] = src[i];
+}
+
+// (2) + (3) speculative walk (pass 0) and synchronisation
+__global__ void __launch_bounds__(kJdLanes) jd_sync_kernel(JdWs e, JdGeom g, int pass) {
+  __shared__ uint32_t huff[kJdHuffWords];
+  __shared__ uint32_t sh_exit[kJdLanes];
+  const int64_t total = e.scal[2];
+  const int t = threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * kJdLanes + t;
+  if ((int64_t)blockIdx.x * kJdLanes >= total) return;
+  if (pass > 0 && ((int)blockIdx.x < pass || e.flags[pass - 1] == 0)) return;
+  jd_load_tabs(e.tabs, huff);
+  const JdHuff* tabs = (const JdHuff*)huff;
+  const uint32_t* words = e.clean;
+  const bool valid = i < total;
+  JdLane l;
+  uint32_t ex = 0, cnt = 0, lastin = 0;
+  if (valid) {
+    l = jd_lane(g, e.seg_start, e.sub_base, i);
+    if (pass == 0) {
+      ex = jd_walk(words, tabs, g, jd_unpack(0, l.boundary), l.limit, l.end, &cnt);
+    } else {
+      ex = e.gexit[i];
+      cnt = e.gcnt[i];
+      lastin = e.glastin[i];
+    }
+  }
+  const uint32_t ex0 = ex;
+  // the previous workgroup's last exit state: unknown in pass 0 (the assumed state stays), and read
+  // once in later passes (a value of this pass or of the one before; flags[] sends a further pass
+  // whenever one changed)
+  const uint32_t head = (pass == 0 || i == 0 || !valid) ? lastin : e.gexit[i - 1];
+  sh_exit[t] = ex;
+  __syncthreads();
+  bool dirty = pass == 0;
+  for (int round = 0; round <= kJdLanes; ++round) {
+    uint32_t in = lastin;
+    if (valid) in = l.q == 0 ? 0u : (t == 0 ? head : sh_exit[t - 1]);
+    const bool changed = valid && in != lastin;
+    __syncthreads();
+    if (changed) {
+      lastin = in;
+      if (in == kJdEnd) {
+        ex = kJdEnd;
+        cnt = 0;
+      } else {
+        ex = jd_walk(words, tabs, g, jd_unpack(in, l.boundary), l.limit, l.end, &cnt);
+      }
+      sh_exit[t] = ex;
+      dirty = true;
+    }
+    if (!__syncthreads_or(changed)) break;
+  }
+  if (valid && dirty) {
+    e.gexit[i] = ex;
+    e.gcnt[i] = cnt;
+    e.glastin[i] = lastin;
+  }
+  if (pass == 0) {
+    if (blockIdx.x == 0 && t == 0) e.flags[0] = total > kJdLanes;
+  } else if (t == kJdLanes - 1 && valid && ex != ex0) {
+    e.flags[pass] = 1;
+  }
+}
+
+// (4) one workgroup: P[i] = blocks completed by the lanes before lane i
+__global__ void __launch_bounds__(1024) jd_place_kernel(JdWs e) {
+  __shared__ int64_t sh[1024];
+  const int64_t total = e.scal[2];
+  int64_t carry = 0;
+  for (int64_t base = 0; base < total; base += 1024) {
+    const int64_t i = base + threadIdx.x;
+    int64_t tot;
+    const int64_t ex = block_excl_scan_op<1024>(i < total ? (int64_t)e.gcnt[i] : 0, (int64_t)0, sh, &tot, OpAdd64());
+    if (i < total) e.P[i] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) e.P[total] = carry;
+}
+
+// (5) the true walk of every lane, storing
+__global__ void __launch_bounds__(kJdLanes) jd_write_kernel(JdWs e, JdGeom g, int16_t* __restrict__ coefs, int32_t* status) {
+  __shared__ uint32_t huff[kJdHuffWords];
+  const int64_t total = e.scal[2];
+  if ((int64_t)blockIdx.x * kJdLanes >= total) return;
+  jd_load_tabs(e.tabs, huff);
+  const int64_t i = (int64_t)blockIdx.x * kJdLanes + threadIdx.x;
+  if (i >= total) return;
+  const JdLane l = jd_lane(g, e.seg_start, e.sub_base, i);
+  const uint32_t in = l.q == 0 ? 0u : e.gexit[i - 1];
+  const int err = jd_walk_store(e.clean, (const JdHuff*)huff, g, jd_unpack(in, l.boundary), in == kJdEnd, l.limit, l.end,
+                                e.P[i] - e.P[e.sub_base[l.seg]], l.quota, l.seg_first, l.last, coefs);
+  if (err) atomicOr(status, err);
+}
+
+// (6) DC prediction. Tiles of 256 scan-order blocks of one component; MODE 0: the tile's (reset seen,
+// sum since it) pair; MODE 1: the running sums with the carry of the tiles before, truncated to int16
+template <int MODE>
+__global__ void __launch_bounds__(256) jd_dc_kernel(JdWs e, JdGeom g, int16_t* __restrict__ coefs) {
+  __shared__ JdSeg sh[256];
+  int64_t tile = blockIdx.x;
+  int c = 0;
+  while (c < 2 && tile >= e.ntile[c]) tile -= e.ntile[c++];
+  const int64_t ne = (int64_t)g.bw[c] * (g.nblk / g.bpm / g.mcux) * g.v[c];
+  const int64_t el = tile * 256 + threadIdx.x;
+  JdSeg x{0, 0};
+  int64_t off = 0;
+  if (el < ne) {
+    int reset;
+    off = jd_dc_off(g, c, el, &reset);
+    x.f = reset;
+    x.v = coefs[off];
+  }
+  const int t = threadIdx.x;
+  sh[t] = x;
+  __syncthreads();
+#pragma unroll
+  for (int o = 1; o < 256; o <<= 1) {
+    JdSeg a{0, 0};
+    if (t >= o) a = sh[t - o];
+    __syncthreads();
+    if (t >= o) sh[t] = jd_seg_combine(a, sh[t]);
+    __syncthreads();
+  }
+  const JdSeg inc = sh[t];
+  if (MODE == 0) {
+    if (t == 255) {
+      e.tile_f[blockIdx.x] = inc.f;
+      e.tile_v[blockIdx.x] = inc.v;
+    }
+  } else if (el < ne) {
+    const JdSeg r = jd_seg_combine(JdSeg{0, e.carry[blockIdx.x]}, inc);
+    coefs[off] = (int16_t)r.v;
+  }
+}
+
+// one workgroup: carry[t] = the running sum entering tile t
+__global__ void __launch_bounds__(1024) jd_dc_carry_kernel(JdWs e, int64_t ntiles) {
+  __shared__ JdSeg sh[1024];
+  const int t = threadIdx.x;
+  JdSeg run{0, 0};
+  for (int64_t base = 0; base < ntiles; base += 1024) {
+    const int64_t i = base + t;
+    JdSeg x{0, 0};
+    if (i < ntiles) x = JdSeg{e.tile_f[i], e.tile_v[i]};
+    sh[t] = x;
+    __syncthreads();
+#pragma unroll
+    for (int o = 1; o < 1024; o <<= 1) {
+      JdSeg a{0, 0};
+      if (t >= o) a = sh[t - o];
+      __syncthreads();
+      if (t >= o) sh[t] = jd_seg_combine(a, sh[t]);
+      __syncthreads();
+    }
+    JdSeg before = run;
+    if (t > 0) before = jd_seg_combine(run, sh[t - 1]);
+    if (i < ntiles) e.carry[i] = before.v;
+    run = jd_seg_combine(run, sh[1023]);
+    __syncthreads();
+  }
+}
+
+static const char* jd_prepare(const mx_jpeg_info* info, int64_t nbytes, JdGeom* g) {
+  if (!info) return "null info";
+  if (nbytes <= 0 || nbytes >= ((int64_t)1 << 31)) return "nbytes must be 1 .. 2^31 - 1";
+  return jpeg_dec_geom(info, jpeg_dec_subseq(), g);
+}
+
+}  // namespace mx
+
+extern "C" size_t mx_jpeg_entropy_decode_workspace(const mx_jpeg_info* info, int64_t nbytes) {
+  JdGeom g;
+  if (jd_prepare(info, nbytes, &g)) return 0;
+  return jd_ws(info, g, nbytes, nullptr, 0).bytes;
+}
+
+extern "C" int mx_jpeg_entropy_decode(const uint8_t* scan, int64_t nbytes, const mx_jpeg_info* info, void* ws,
+                                      size_t ws_bytes, int16_t* coefs, int32_t* status, mx_stream_t stream) {
+  MX_CHECK_ARG(scan && info && ws && coefs && status, "jpeg_entropy_decode: null argument");
+  JdGeom g;
+  const char* bad = jd_prepare(info, nbytes, &g);
+  MX_CHECK_ARG(!bad, "jpeg_entropy_decode: %s", bad);
+  MX_CHECK_ARG(((uintptr_t)coefs & 15) == 0 && ((uintptr_t)ws & 255) == 0 && ((uintptr_t)status & 3) == 0,
+               "jpeg_entropy_decode: coefficients must be 16-byte, the workspace 256-byte and the status 4-byte aligned");
+  const JdWs e = jd_ws(info, g, nbytes, ws, ws_bytes);
+  MX_CHECK_ARG(e.bytes <= ws_bytes, "jpeg_entropy_decode: workspace of %lld bytes required", (long long)e.bytes);
+  JdHuff tabs[kJdTables];
+  MX_CHECK_ARG(jpeg_dec_tables(info, tabs), "jpeg_entropy_decode: bad Huffman table");
+  hipStream_t st = (hipStream_t)stream;
+  const int mis = (int)((uintptr_t)scan & 15);
+  const int64_t nchunk = cdiv(nbytes + mis, kJdChunk);
+  MX_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+  MX_HIP(hipMemsetAsync(e.flags, 0, sizeof(uint32_t) * (size_t)(e.nwg + 1), st));
+  MX_HIP(hipMemsetAsync(coefs, 0, sizeof(int16_t) * (size_t)info->coef_total, st));
+  for (int c = 0; c < 3; ++c) {
+    JdHuffPair p;
+    p.t[0] = tabs[2 * c];
+    p.t[1] = tabs[2 * c + 1];
+    jd_tables_kernel<<<1, 256, 0, st>>>(p, e.tabs + 2 * c);
+    MX_LAUNCH_CHECK();
+  }
+  jd_mark_kernel<<<(unsigned)nchunk, 256, 0, st>>>(scan, nbytes, mis, e);
+  MX_LAUNCH_CHECK();
+  jd_scan_chunks_kernel<<<1, 1024, 0, st>>>(e, nchunk, g.nseg, status);
+  MX_LAUNCH_CHECK();
+  jd_compact_kernel<<<(unsigned)nchunk, 256, 0, st>>>(scan, nbytes, mis, e, g.nseg);
+  MX_LAUNCH_CHECK();
+  jd_seg_kernel<<<1, 1024, 0, st>>>(e, g.nseg, g.subseq, status);
+  MX_LAUNCH_CHECK();
+  for (int64_t pass = 0; pass < e.nwg; ++pass) {
+    jd_sync_kernel<<<(unsigned)e.nwg, kJdLanes, 0, st>>>(e, g, (int)pass);
+    MX_LAUNCH_CHECK();
+  }
+  jd_place_kernel<<<1, 1024, 0, st>>>(e);
+  MX_LAUNCH_CHECK();
+  jd_write_kernel<<<(unsigned)e.nwg, kJdLanes, 0, st>>>(e, g, coefs, status);
+  MX_LAUNCH_CHECK();
+  jd_dc_kernel<0><<<(unsigned)e.ntiles, 256, 0, st>>>(e, g, coefs);
+  MX_LAUNCH_CHECK();
+  jd_dc_carry_kernel<<<1, 1024, 0, st>>>(e, e.ntiles);
+  MX_LAUNCH_CHECK();
+  jd_dc_kernel<1><<<(unsigned)e.ntiles, 256, 0, st>>>(e, g, coefs);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

@@ -107,6 +107,10 @@ _SIGS = {
     "mx_jpeg_decode_coefs": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "mx_jpeg_workspace": (c_sz, [c_vp]),
     "mx_jpeg_reconstruct": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "mx_jpeg_entropy_decode_workspace": (c_sz, [c_vp, c_i64]),
+    "mx_jpeg_entropy_decode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "mx_jpeg_entropy_decode_set_subseq": (c_int, [c_int]),
+    "mx_jpeg_decode_coefs_chunked": (c_int, [c_vp, c_i64, c_vp, c_int, c_vp, c_vp]),
     "mx_jpeg_encode_info": (c_int, [c_int, c_int, c_int, c_int, c_vp]),
     "mx_jpeg_write_header": (c_int, [c_vp, c_vp, c_i64, c_vp]),
     "mx_jpeg_scan_bound": (c_i64, [c_vp]),

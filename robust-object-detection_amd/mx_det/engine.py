@@ -393,7 +393,7 @@ class DeviceJpegLoader:
     def _one(self, b):
         from . import jpeg
         try:
-            return jpeg.decode(b, self.dev)
+            return jpeg.decode(b, self.dev, entropy=jpeg.env_entropy())
         except (jpeg.JpegUnsupported, ValueError):
             # unsupported coding, or a stream the strict parser rejects but libjpeg decodes with a
             # warning: decode on the host exactly as the reference does (PIL raises if it cannot)
@@ -410,12 +410,14 @@ class DeviceJpegLoader:
         return len(self.loader)
 
 
-def _host_decode(b):
+def _host_decode(b, entropy="host"):
     """Host half of one image's decode (a prefetch thread): JPEG -> (info, pinned coefficients), or
-    for files the hybrid decoder does not handle, PIL's RGB pixels (the reference's decode)."""
+    for files the hybrid decoder does not handle, PIL's RGB pixels (the reference's decode). With
+    entropy="device" (MX_JPEG_DECODE=device) the host half is the parse plus pinning the file's bytes:
+    (info, pinned bytes)."""
     from . import jpeg
     try:
-        return jpeg.host_stage(b)
+        return jpeg.host_stage_bytes(b) if entropy == "device" else jpeg.host_stage(b)
     except (jpeg.JpegUnsupported, ValueError):
         import io
         from PIL import Image
@@ -487,6 +489,7 @@ class PrefetchJpegLoader:
         from . import jpeg
         q = queue.Queue(maxsize=max(1, self.depth))
         stop = threading.Event()
+        entropy = jpeg.env_entropy()
         # the producer's Python work must not hold the GIL for a whole 5 ms switch interval while
         # the training thread waits to issue launches
         old_switch = sys.getswitchinterval()
@@ -505,7 +508,9 @@ class PrefetchJpegLoader:
             try:
                 with ThreadPoolExecutor(max(1, self.workers)) as pool:
                     for images, targets in self.loader:
-                        futs = [pool.submit(_host_decode, b) for b in images]
+                        futs = [pool.submit(_host_decode, b, entropy) for b in images]
+                        if entropy == "device":  # the files stay at hand: a flagged one is decoded on the host
+                            futs = (futs, images)
                         if not put((futs, _pack_targets(targets))):
                             return
             except BaseException as e:  # surfaced in the consuming thread
@@ -534,7 +539,39 @@ class PrefetchJpegLoader:
                     pass
             return False
 
+        def stage_device_entropy(item):
+            """stage() with the entropy decode on the device: every image's status word lands in one
+            int32 tensor, read once after the batch's event; flagged images are decoded again by the
+            host path and the event re-recorded. No per-image synchronisation."""
+            (futs, files), (tbuf, layout) = item
+            done = [f.result() for f in futs]
+            with capture_lock, torch.cuda.device(self.dev), torch.cuda.stream(ls):
+                status = torch.zeros(len(done), dtype=torch.int32, device=self.dev)
+                imgs, redo = [], []
+                for k, (info, host) in enumerate(done):
+                    if info is None:
+                        imgs.append(torch.from_numpy(host).to(self.dev))
+                        continue
+                    r = jpeg.device_stage_bytes(info, host, self.dev, status=status[k:k + 1])
+                    imgs.append(None if r is None else r[0])
+                    if r is None:
+                        redo.append(k)
+                tg = _unpack_targets(tbuf.to(self.dev, non_blocking=True), layout)
+                ev = torch.cuda.Event()
+                ev.record(ls)
+                ev.synchronize()
+                redo += [k for k in torch.nonzero(status.cpu()).flatten().tolist() if k not in redo]
+                for k in redo:
+                    info, host = _host_decode(files[k])
+                    imgs[k] = torch.from_numpy(host).to(self.dev) if info is None else jpeg.device_stage(info, host, self.dev)
+                if redo:
+                    ev = torch.cuda.Event()
+                    ev.record(ls)
+            return imgs, tg, ev
+
         def stage(item):
+            if entropy == "device":
+                return stage_device_entropy(item)
             futs, (tbuf, layout) = item
             done = [f.result() for f in futs]
             with capture_lock, torch.cuda.device(self.dev), torch.cuda.stream(ls):

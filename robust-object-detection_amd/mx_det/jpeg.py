@@ -1,17 +1,27 @@
-"""Baseline-JPEG decode onto the device, hybrid like a host-entropy /
-device-pixel decoder: the Huffman-coded bitstream is decoded on the host (libmx_det
-mx_jpeg_decode_coefs: the sequential prefix code has no parallel structure without restart markers),
-the quantised coefficients (int16, ~1.5 B per pixel at 4:2:0) are copied to HBM, and the device
-dequantises, runs the libjpeg islow IDCT, upsamples the chroma and converts YCbCr -> RGB
-(mx_jpeg_reconstruct). Output: uint8 [H, W, 3] on the device, bit-identical to libjpeg-turbo's default
-decode -- PIL Image.open(p).convert("RGB") (coco_detection_dataset.py:23), or with bgr=True
-cv2.imread (restore_testsets.py:99). Progressive / arithmetic / CMYK / 4:4:0 files raise
+"""Baseline-JPEG decode onto the device. Two ways to the quantised coefficients:
+
+entropy="host" (the default): the Huffman-coded bitstream is decoded on the host (libmx_det
+mx_jpeg_decode_coefs, a sequential bit-at-a-time loop) and the coefficients (int16, ~1.5 B per pixel
+at 4:2:0, about four times the file's size) are copied to HBM.
+
+entropy="device" (MX_JPEG_DECODE=device for read_file and the loaders): only the file's bytes are
+copied and mx_jpeg_entropy_decode decodes the scan on the device. The scan does have parallel
+structure, restart markers or not: a Huffman stream re-synchronises, so lanes decode fixed-size
+subsequences speculatively and a fix-up iteration makes the result the sequential decoder's, bit for
+bit. A stream the device decoder flags (truncated, corrupt: a non-zero status word) is decoded by the
+host path, so results and exceptions are those of entropy="host" for every input.
+
+Either way the device then dequantises, runs the libjpeg islow IDCT, upsamples the chroma and converts
+YCbCr -> RGB (mx_jpeg_reconstruct). Output: uint8 [H, W, 3] on the device, bit-identical to
+libjpeg-turbo's default decode -- PIL Image.open(p).convert("RGB") (coco_detection_dataset.py:23), or
+with bgr=True cv2.imread (restore_testsets.py:99). Progressive / arithmetic / CMYK / 4:4:0 files raise
 NotImplementedError (MX_EUNSUPPORTED); callers that must accept them decode those on the host.
 
 Encode (encode / write_file / encode_coefs, below) runs wholly on the device -- pixel stage and
 entropy coder -- and is byte-identical to PIL's Image.save(format="JPEG", quality, subsampling).
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -68,33 +78,131 @@ def host_stage(data):
     return decode_coefs(data, info, out=host)
 
 
+def _reconstruct(info, dev, device, bgr):
+    ws = torch.empty(_lib.load().mx_jpeg_workspace(ctypes.byref(info)), dtype=torch.uint8, device=device)
+    out = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=device)
+    _lib.call("mx_jpeg_reconstruct", dev.data_ptr(), ctypes.byref(info), ws.data_ptr(), ws.numel(), out.data_ptr(),
+              int(bool(bgr)), _lib.stream())
+    return out
+
+
 def device_stage(info, host, device, bgr=False):
     """The device half: coefficients to HBM (non-blocking from pinned memory), then dequantise + islow
     IDCT + chroma upsampling + YCbCr -> RGB in mx_jpeg_reconstruct on the current stream."""
-    dev = host.to(device, non_blocking=True)
-    ws = torch.empty(_lib.load().mx_jpeg_workspace(ctypes.byref(info)), dtype=torch.uint8, device=device)
-    out = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=device)
-    _lib.call("mx_jpeg_reconstruct", dev.data_ptr(), ctypes.byref(info), ws.data_ptr(), ws.numel(), out.data_ptr(),
-              int(bool(bgr)), _lib.stream())
-    return out
+    return _reconstruct(info, host.to(device, non_blocking=True), device, bgr)
 
 
-def decode(data, device, bgr=False, pin=True):
-    """JPEG bytes -> uint8 [H, W, 3] tensor on `device` (RGB, or BGR with bgr=True)."""
+def env_entropy():
+    """Where read_file, the loaders (mx_det.engine) and the offline scripts decode the scan:
+    MX_JPEG_DECODE = host (the default) or device."""
+    mode = os.environ.get("MX_JPEG_DECODE", "host")
+    if mode not in ("host", "device"):
+        raise ValueError("MX_JPEG_DECODE is 'host' or 'device'")
+    return mode
+
+
+def set_subseq(bits):
+    """Bits one lane of the device entropy decoder walks (64 .. 65536, default 512): a process setting,
+    results identical."""
+    if _lib.load().mx_jpeg_entropy_decode_set_subseq(int(bits)) != 0:
+        raise ValueError(_lib.load().mx_last_error().decode())
+
+
+def decode_coefs_chunked(data, subseq_bits=0, info=None):
+    """The device entropy decoder's passes run serially on the host (mx_jpeg_decode_coefs_chunked, the
+    CPU reference of the kernels) -> (info, int16 [coef_total], status)."""
+    info = parse(data) if info is None else info
+    buf = np.frombuffer(data, dtype=np.uint8)
+    coefs = np.empty(info.coef_total, dtype=np.int16)
+    status = ctypes.c_int32(0)
+    rc = _lib.load().mx_jpeg_decode_coefs_chunked(buf.ctypes.data, buf.size, ctypes.byref(info), int(subseq_bits),
+                                                  coefs.ctypes.data, ctypes.byref(status))
+    if rc != 0:
+        raise ValueError(_lib.load().mx_last_error().decode())
+    return info, coefs, status.value
+
+
+def _pin_bytes(data):
+    from .conv import capture_lock
+    buf = np.frombuffer(data, dtype=np.uint8)
+    with capture_lock:  # see host_stage
+        host = torch.empty(buf.size, dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:] = buf
+    return host
+
+
+def host_stage_bytes(data):
+    """The host half with the entropy decode on the device: marker parse + the file's bytes in pinned
+    memory -> (info, pinned uint8 tensor). Thread-safe."""
+    return parse(data), _pin_bytes(data)
+
+
+def entropy_stage(info, host, device, status=None, offset=0):
+    """File bytes (a CPU uint8 tensor, pinned for a non-blocking copy) to HBM -- the file's size, not
+    coef_total * 2 bytes -- and mx_jpeg_entropy_decode on the current stream -> (int16 [coef_total]
+    device tensor, status), or None when the entry point refuses the file (a Huffman table the host
+    decoder rejects too). status: a one-element int32 device tensor to fill (a slot of a batch's status
+    words), allocated when None; 0 means the coefficients are mx_jpeg_decode_coefs', anything else that
+    the host must decode the file. No host synchronisation. offset: extra bytes in front of the device
+    copy (tests: the scan at another alignment)."""
+    lib = _lib.load()
+    n = host.numel()
+    dev = torch.empty(offset + n, dtype=torch.uint8, device=device)
+    dev[offset:].copy_(host, non_blocking=True)
+    nscan = n - info.scan_off
+    ws = torch.empty(max(int(lib.mx_jpeg_entropy_decode_workspace(ctypes.byref(info), nscan)), 1), dtype=torch.uint8,
+                     device=device)
+    coefs = torch.empty(info.coef_total, dtype=torch.int16, device=device)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=device)
+    rc = lib.mx_jpeg_entropy_decode(dev.data_ptr() + offset + info.scan_off, nscan, ctypes.byref(info), ws.data_ptr(),
+                                    ws.numel(), coefs.data_ptr(), status.data_ptr(), _lib.stream())
+    if rc == -1:
+        return None
+    if rc != 0:
+        raise _lib.MxError(f"mx_jpeg_entropy_decode failed ({rc}): {lib.mx_last_error().decode()}")
+    return coefs, status
+
+
+def device_stage_bytes(info, host, device, bgr=False, status=None):
+    """The device half with the entropy decode on the device: entropy_stage + mx_jpeg_reconstruct ->
+    (uint8 [H, W, 3], status), or None (see entropy_stage). The image is valid where the status reads 0."""
+    r = entropy_stage(info, host, device, status)
+    if r is None:
+        return None
+    return _reconstruct(info, r[0], device, bgr), r[1]
+
+
+def decode_coefs_device(data, device, info=None):
+    """Device entropy decode -> (info, int16 [coef_total] device tensor, int32 [1] device status tensor;
+    0: the coefficients equal decode_coefs'). The file's bytes go up as one pinned, non-blocking copy."""
+    info = parse(data) if info is None else info
+    r = entropy_stage(info, _pin_bytes(data), device)
+    if r is None:
+        raise ValueError(_lib.load().mx_last_error().decode())
+    return info, r[0], r[1]
+
+
+def decode(data, device, bgr=False, pin=True, entropy="host"):
+    """JPEG bytes -> uint8 [H, W, 3] tensor on `device` (RGB, or BGR with bgr=True). entropy="device":
+    the parse on the host, the entropy decode and the reconstruction on the device, then one read of
+    the status word; a flagged file goes through the host path, so results and exceptions are those of
+    entropy="host" for every input."""
+    if entropy not in ("host", "device"):
+        raise ValueError("decode: entropy is 'host' or 'device'")
+    if entropy == "device":
+        r = device_stage_bytes(*host_stage_bytes(data), device, bgr)
+        if r is not None and int(r[1].item()) == 0:
+            return r[0]
     if pin:
         return device_stage(*host_stage(data), device, bgr)
     info, coefs = decode_coefs(data)
-    dev = torch.from_numpy(coefs).to(device)
-    ws = torch.empty(_lib.load().mx_jpeg_workspace(ctypes.byref(info)), dtype=torch.uint8, device=device)
-    out = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device=device)
-    _lib.call("mx_jpeg_reconstruct", dev.data_ptr(), ctypes.byref(info), ws.data_ptr(), ws.numel(), out.data_ptr(),
-              int(bool(bgr)), _lib.stream())
-    return out
+    return _reconstruct(info, torch.from_numpy(coefs).to(device), device, bgr)
 
 
 def read_file(path, device, bgr=False):
     with open(path, "rb") as f:
-        return decode(f.read(), device, bgr=bgr)
+        return decode(f.read(), device, bgr=bgr, entropy=env_entropy())
 
 
 # ------------------------------------------------------------------------------------------ encode

@@ -70,12 +70,12 @@ def corrupt(img_bgr, variant):
 
 def _read_bgr(path):
     """cv2.imread(path) on the device: BGR uint8 [H, W, 3]; None for unreadable files (skipped, like
-    cv2.imread's None)."""
+    cv2.imread's None). MX_JPEG_DECODE=device decodes the scan on the device too."""
     dev = torch.device("cuda", torch.cuda.current_device())
     try:
         data = Path(path).read_bytes()
         try:
-            return jpeg.decode(data, dev, bgr=True)
+            return jpeg.decode(data, dev, bgr=True, entropy=jpeg.env_entropy())
         except (jpeg.JpegUnsupported, ValueError):
             with Image.open(path) as im:
                 rgb = np.ascontiguousarray(np.asarray(im.convert("RGB"))[..., ::-1])

@@ -4,7 +4,8 @@ Reference restore_testsets.py:82-159: Noise / Blur / LowRes images restored, ann
 copied unchanged; JPEG output. Here the restoration runs on the GPU (mx_det.unet.restore_u8), and so
 do the JPEG decode (mx_det.jpeg.read_file; PIL for the files it does not handle) and the quality-95
 encode (mx_det.jpeg.write_file), both bit-identical to libjpeg-turbo: pixels never visit the host.
-MX_JPEG_ENCODE=host encodes with PIL instead. The fused eval path (eval_restored.py) skips this step.
+MX_JPEG_ENCODE=host encodes with PIL instead; MX_JPEG_DECODE=device decodes the scan on the device
+too (the default decodes it on the host). The fused eval path (eval_restored.py) skips this step.
 """
 import os
 import shutil
