@@ -274,6 +274,8 @@ int mx_resize_normalize_pad_f32(const float* const* imgs_chw, const int64_t* Hs,
  *   wgrad: dw[K,R,S,C] f32 = sum over N,Ho,Wo dy (x) x      (overwritten; the pixel axis is split
  *          into per-split partials in a workspace and summed by a reduce kernel — no atomics)
  *   C % 8 == 0 is required (the stem input is padded to 8 channels).
+ *   stride_h / stride_w, pad_h / pad_w and R / S are independent (asymmetric strides, pads and
+ *   filters are supported by every pass); an output map may be smaller than the filter.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
   int64_t N, H, W, C, K, R, S, Ho, Wo;
@@ -395,6 +397,16 @@ int mx_conv_set_korder(int order);
 /* Timing experiments only: 1 = the bf16x3 buffer kernels skip their epilogue (outputs undefined). */
 int mx_conv_set_debug(int v);
 int mx_conv_set_wgrad_target(int64_t blocks);
+/* The calling thread's last conv launch (fwd / dgrad / wgrad, bf16 and bf16x3 entries), for tests that
+ * assert which path a shape took: out[0] pass (0 fwd, 1 dgrad, 2 wgrad), out[1] x out[2] block tile
+ * (rows x columns), out[3] K splits (wgrad: pixel splits) launched, out[4] output tiles, out[5] 1 when
+ * a buffer-descriptor kernel ran, out[6] kernel kind (bf16 fwd/dgrad: the mx_conv_set_variant number
+ * launched; bf16 wgrad: the mx_conv_set_wgrad_variant number launched, 0 when the buffer kernel's map
+ * guard fell back to the register kernel; bf16x3 fwd/dgrad: 100 + the mx_conv_set_stages alternative;
+ * bf16x3 wgrad: 103 / 104 / 105 for the 128x128 / 128x256 / 256x256 block), out[7] launches the entry
+ * has issued (stride-2 dgrad: the non-empty parity classes; the record is that of the last one).
+ * MX_EINVAL before the thread's first launch. */
+int mx_conv_last_launch(int32_t out[8]);
 
 /* ---------------------------------------------------------------------------------------------
  * Precision-faithful convolution (bf16x3): the reference trains and evaluates its convs in fp32

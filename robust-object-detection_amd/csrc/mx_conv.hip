@@ -2937,6 +2937,27 @@ extern "C" int64_t mx_conv_mblocks(const mx_conv_shape* s) { return cdiv(s->N * 
 // direct-to-LDS wgrad), 3..6 multi-stage direct-to-LDS, 7 (default) per-launch choice of 3 / 4.
 static int g_conv_variant = 7;
 
+// The last conv launch of the calling thread (mx_conv_last_launch): written by launch_igemm,
+// launch_igemm_x3 and the two wgrad entries, so a test can assert the path a shape really took.
+// [0] pass (0 fwd, 1 dgrad, 2 wgrad), [1] block rows, [2] block columns, [3] K / pixel splits launched,
+// [4] output tiles, [5] 1 = buffer-descriptor kernel, [6] kernel kind (bf16 fwd/dgrad: the variant
+// 0..9 launched; bf16 wgrad: 0 px32, 1 px64, 2 direct-to-LDS, 3 buffer; bf16x3: 100 + the ring /
+// wave-tile alternative (mx_conv_set_stages) for fwd/dgrad, 100 + 3 / 4 / 5 (128x128, 128x256,
+// 256x256 block) for wgrad), [7] launches issued by the entry so far (dgrad: non-empty parity classes)
+static thread_local int32_t g_last_launch[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
+static thread_local int32_t g_launch_count = 0;  // reset by each entry point, counted per launch
+static void record_launch(int pass, int bmt, int bn, int64_t splits, int64_t tiles, bool buf, int kind) {
+  int32_t* r = g_last_launch;
+  r[0] = pass; r[1] = bmt; r[2] = bn; r[3] = (int32_t)splits; r[4] = (int32_t)tiles; r[5] = buf ? 1 : 0; r[6] = kind;
+  r[7] = ++g_launch_count;
+}
+extern "C" int mx_conv_last_launch(int32_t out[8]) {
+  MX_CHECK_ARG(out, "mx_conv_last_launch: null output");
+  MX_CHECK_ARG(g_last_launch[0] >= 0, "mx_conv_last_launch: no conv launched on this thread yet");
+  for (int i = 0; i < 8; ++i) out[i] = g_last_launch[i];
+  return MX_OK;
+}
+
 // GEMM geometry of one launch and its split-K factor: grids that would leave the chip under-filled
 // (< ~1.25 blocks per CU) split the K loop, keeping >= 4 K-tiles (of 64) per split.
 struct Geo {
@@ -3103,6 +3124,7 @@ extern "C" size_t mx_conv_workspace(const mx_conv_shape* s, int pass) {
   const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
   size_t mx = 0;
   for (int i = 0; i < n; ++i) {
+    if (cl[i].Hc * cl[i].Wc == 0) continue;  // an empty parity class (H or W of 1) is not launched
     Geo g = make_geo(s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
     if (g.splits > 1) mx = std::max(mx, sizeof(float) * (size_t)g.splits * g.M * g.Ncol);
   }
@@ -3196,6 +3218,7 @@ static int launch_igemm(ConvP& p, const Geo& g, void* ws, size_t ws_bytes, hipSt
   else if (g.narrow) launch_variant<64, MODE>(v, p, blocks, st);
   else launch_variant<128, MODE>(v, p, blocks, st);
   MX_LAUNCH_CHECK();
+  record_launch(MODE, g.bmt, g.bn, p.splits, g.tiles, buf, buf ? 3 : (g.bn == 256 ? 9 : v));
   if (p.slab) {
     // the reduce works in 128-row blocks; 16-column blocks when 64-column ones would not fill the chip
     if (cdiv(g.M, BM) * cdiv(g.Ncol, 64) >= 2 * (int64_t)num_cus()) {
@@ -3248,6 +3271,7 @@ extern "C" int mx_conv2d_fwd_ex(const mx_conv_shape* s, const uint16_t* x, const
   p.bias = bias; p.residual = residual; p.act = act; p.out = y; p.out_f32 = ydtype == MX_F32;
   p.stats = stats; p.mblocks = cdiv(p.M, SROWS);
   p.src_elems = s->N * s->H * s->W * s->C; p.wt_elems = p.Ncol * p.Kdim;
+  g_launch_count = 0;
   return launch_igemm<0>(p, make_geo(p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -3478,6 +3502,7 @@ static int dgrad_impl(const mx_conv_shape* s, const uint16_t* dy, const uint16_t
   int br[4], bs[4];
   const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
   const bool remap = s->stride_h > 1 || s->stride_w > 1;
+  g_launch_count = 0;
   for (int i = 0; i < n; ++i) {
     const DClass& c = cl[i];
     if (c.Hc * c.Wc == 0) continue;
@@ -3637,6 +3662,8 @@ extern "C" int mx_conv2d_wgrad_ex(const mx_conv_shape* s, const uint16_t* dy, co
   else if (v == 1) conv_wgrad_kernel<64><<<grid, NT, 0, st>>>(p);
   else conv_wgrad_kernel<32><<<grid, NT, 0, st>>>(p);
   MX_LAUNCH_CHECK();
+  g_launch_count = 0;
+  record_launch(2, 128, 128, g.splits, g.tiles, v == 3, v);
   if (g.splits > 1) {
     MX_CHECK_ARG(Kout < 65536, "conv wgrad: too many output channels for the split reduce");
     wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);
@@ -3690,6 +3717,8 @@ static Geo make_geo_x3(int64_t M, int64_t Ncol, int64_t Kdim) {
     g.splits = (int)std::max<int64_t>(1, sp);
   }
   if (g_max_splits && g.splits > g_max_splits) g.splits = g_max_splits;
+  // the splits the launch fills (equal shares of whole K-tiles): the workspace holds no unused slab
+  if (g.splits > 1) g.splits = (int)cdiv(g.nk, cdiv(g.nk, (int64_t)g.splits));
   return g;
 }
 
@@ -3767,6 +3796,7 @@ static int launch_igemm_x3(ConvP& p, const Geo& g0, void* ws, size_t ws_bytes, h
     else launch_x3<128, MODE, 128>(p, blocks, st);
   }
   MX_LAUNCH_CHECK();
+  record_launch(MODE, g.bmt, g.bn, p.splits, g.tiles, buf, 100 + (buf ? g_buf_stages : 0));
   if (p.slab) {
     if (cdiv(g.M, BM) * cdiv(g.Ncol, 64) >= 2 * (int64_t)num_cus()) {
       dim3 rg((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.Ncol, 64));
@@ -3819,6 +3849,7 @@ extern "C" size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass) {
   const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
   size_t mx = 0;
   for (int i = 0; i < n; ++i) {
+    if (cl[i].Hc * cl[i].Wc == 0) continue;  // an empty parity class (H or W of 1) is not launched
     const Geo g = make_geo_x3(s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
     if (g.splits > 1) mx = std::max(mx, sizeof(float) * (size_t)g.splits * g.M * g.Ncol);
   }
@@ -3841,6 +3872,7 @@ extern "C" int mx_conv2d_fwd_x3(const mx_conv_shape* s, const float* x, const ui
   p.bias = bias; p.residual = residual; p.act = act; p.out = y; p.out_f32 = 1;
   p.stats = stats; p.mblocks = cdiv(p.M, SROWS);
   p.src_elems = s->N * s->H * s->W * s->C; p.wt_elems = p.Ncol * p.Kdim; p.wt_plane = p.Ncol * p.Kdim;
+  g_launch_count = 0;
   return launch_igemm_x3<0>(p, make_geo_x3(p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -3863,6 +3895,7 @@ extern "C" int mx_conv2d_dgrad_x3(const mx_conv_shape* s, const float* dy, const
   const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
   const bool remap = s->stride_h > 1 || s->stride_w > 1;
   const int64_t plane = s->C * s->R * s->S * s->K;
+  g_launch_count = 0;
   for (int i = 0; i < n; ++i) {
     const DClass& c = cl[i];
     if (c.Hc * c.Wc == 0) continue;
@@ -3924,6 +3957,9 @@ extern "C" int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const
   else
     conv_wgrad_x3_kernel<<<(unsigned)(g.tiles * g.splits), NT, 2 * 4 * 32 * 256, st>>>(p);
   MX_LAUNCH_CHECK();
+  g_launch_count = 0;
+  record_launch(2, wgrad_x3_ww() ? 256 : 128, (wgrad_x3_ww() || wgrad_x3_wide()) ? 256 : 128, g.splits, g.tiles, true,
+                100 + (wgrad_x3_ww() ? 5 : wgrad_x3_wide() ? 4 : 3));
   if (g.splits > 1) {
     MX_CHECK_ARG(Kout < 65536, "conv wgrad x3: too many output channels for the split reduce");
     wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);

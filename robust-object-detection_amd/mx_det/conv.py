@@ -103,6 +103,17 @@ def shape(x_nhwc, K, R, S, stride, pad):
     return _lib.ConvShape(N, H, W, C, K, R, S, Ho, Wo, stride[0], stride[1], pad[0], pad[1])
 
 
+_LAUNCH_FIELDS = ("pass_", "bmt", "bn", "splits", "tiles", "buf", "kind", "launches")
+
+
+def last_launch():
+    """The calling thread's last conv launch (mx_conv_last_launch) as a dict: pass_ (0 fwd, 1 dgrad,
+    2 wgrad), bmt x bn block tile, splits, tiles, buf (buffer-descriptor kernel), kind, launches."""
+    out = (ctypes.c_int32 * 8)()
+    call("mx_conv_last_launch", ctypes.cast(out, ctypes.c_void_p))
+    return dict(zip(_LAUNCH_FIELDS, out))
+
+
 def weight_krsc(w, cin_pad=None):
     """[K,C,R,S] f32 parameter -> [K,R,S,C'] bf16 (C' = cin_pad, zero channels appended)."""
     k = w.detach().permute(0, 2, 3, 1)
