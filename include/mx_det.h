@@ -281,6 +281,21 @@ typedef struct {
   int64_t N, H, W, C, K, R, S, Ho, Wo;
   int32_t stride_h, stride_w, pad_h, pad_w;
 } mx_conv_shape;
+/* Launch settings of ONE call: the six values the per-shape tuner varies. The entries that take a
+ * `const mx_conv_cfg* cfg` (last parameter) read it as follows: NULL = the process defaults (the
+ * mx_conv_set_* values below); otherwise the cfg replaces all six values for that call only and no
+ * process default is read or written for them. A workspace query and the launch that consumes its
+ * workspace must be given the same cfg. A cfg outside the setters' ranges (or reserved != 0) is
+ * MX_EINVAL before any HIP call (workspace queries: 0). The convenience forms without a cfg
+ * parameter use the process defaults. */
+typedef struct mx_conv_cfg {
+  int32_t tile_rows, tile_cols; /* mx_conv_set_tile       (0,0 = automatic) */
+  int32_t max_splits;           /* mx_conv_set_max_splits (0 = automatic)   */
+  int32_t stages;               /* mx_conv_set_stages     (0 = automatic)   */
+  int32_t wgrad_variant;        /* mx_conv_set_wgrad_variant                */
+  int32_t reserved;             /* must be 0 */
+  int64_t wgrad_target;         /* mx_conv_set_wgrad_target (0 = automatic) */
+} mx_conv_cfg;
 int64_t mx_conv_mblocks(const mx_conv_shape* s);
 int mx_conv2d_fwd(const mx_conv_shape* s, const uint16_t* x, const uint16_t* w, const float* bias, void* y,
                   int ydtype, float* stats, mx_stream_t stream);
@@ -297,13 +312,16 @@ int mx_conv2d_dgrad(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* 
  * of a strided conv. */
 int mx_conv2d_fwd_ex(const mx_conv_shape* s, const uint16_t* x, const uint16_t* w, const float* bias,
                      const uint16_t* residual, int act, void* y, int ydtype, float* stats, void* ws, size_t ws_bytes,
-                     mx_stream_t stream);
+                     mx_stream_t stream, const mx_conv_cfg* cfg);
 /* Split workspace for pass 0 (fwd) / 1 (dgrad) / 2 (wgrad): 0 when the grid fills the chip unsplit. */
-size_t mx_conv_workspace(const mx_conv_shape* s, int pass);
-/* Kernel-variant knobs for A/B measurement (process-wide). fwd/dgrad: 0 register-staged,
- * 1/2 direct-to-LDS 2-stage, 3..6 multi-stage direct-to-LDS (BK32x3, BK64x2, BK32x4, BK64x3),
- * 7 (default) per-launch choice between 3 and 4. wgrad: 0 32-pixel K-tiles, 1 (default) 64-pixel,
- * 2 direct-to-LDS. */
+size_t mx_conv_workspace(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg);
+/* Process defaults of the launch settings, for tools and A/B tests: what a call with cfg == NULL
+ * uses. variant, loader and korder are whole-process diagnostics with no per-call form; the others
+ * are the fields of mx_conv_cfg, and a call with a cfg neither reads nor changes them (a tuned launch
+ * does not reset them). fwd/dgrad variant: 0 register-staged, 1/2 direct-to-LDS 2-stage, 3..6
+ * multi-stage direct-to-LDS (BK32x3, BK64x2, BK32x4, BK64x3), 7 (default) per-launch choice between
+ * 3 and 4. wgrad variant: 0 32-pixel K-tiles, 1 64-pixel, 2 direct-to-LDS, 3 (default) buffer
+ * descriptors, 4 / 5 the bf16x3 128x256 / 256x256 blocks (bf16: as 3). */
 int mx_conv_set_variant(int variant);
 int mx_conv_get_variant(void);
 int mx_conv_set_wgrad_variant(int variant);
@@ -366,7 +384,7 @@ int mx_conv2d_dgrad_t(const mx_conv_shape* s, const uint16_t* dy, const uint16_t
  * an input that also feeds another branch (ResNet bottleneck x -> conv1 and x -> + identity, a stage
  * output read by the next stage and the FPN) without a separate add pass. */
 int mx_conv2d_dgrad_ex(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt, const uint16_t* residual,
-                       uint16_t* dx, void* ws, size_t ws_bytes, mx_stream_t stream);
+                       uint16_t* dx, void* ws, size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg);
 /* mx_conv2d_dgrad_ex whose output dx is the incoming gradient of a train-mode BatchNorm (+act)
  * that produced z -> y with batch mean / invstd: the epilogue also writes, per 64-row block, the
  * column sums of g = bf16(dx) * act'(y) and g * (z - mean) * invstd into part [2][part_mb][C]
@@ -374,14 +392,14 @@ int mx_conv2d_dgrad_ex(const mx_conv_shape* s, const uint16_t* dy, const uint16_
  * pass over dx, y, z). Stride 1. */
 int mx_conv2d_dgrad_bnb(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt, const uint16_t* residual,
                         uint16_t* dx, const uint16_t* y, const uint16_t* z, const float* mean, const float* invstd,
-                        int act, float* part, int64_t part_mb, void* ws, size_t ws_bytes, mx_stream_t stream);
+                        int act, float* part, int64_t part_mb, void* ws, size_t ws_bytes, mx_stream_t stream,
+                        const mx_conv_cfg* cfg);
 int mx_conv2d_wgrad(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* x, float* dw, mx_stream_t stream);
 /* Hot-path wgrad: dw written directly in layout 0 ([Kout][R][S][Cin]) or 1 ([Kout][Cin][R][S], the
  * torch parameter layout, so the result is the weight's .grad as is), dropping the zero-padded
  * channels (Kout <= s->K, Cin <= s->C); ws = mx_conv_workspace(s, 2) bytes. */
 int mx_conv2d_wgrad_ex(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* x, float* dw, int64_t Kout,
-                       int64_t Cin, int layout, void* ws, size_t ws_bytes, mx_stream_t stream);
-/* wgrad grid sizing knob: split the pixel axis until ~blocks workgroups (default 512). */
+                       int64_t Cin, int layout, void* ws, size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg);
 /* fwd/dgrad operand loader knob: 1 (default) buffer descriptors with wave-uniform tap offsets where
  * the shape allows (input channels % 32 == 0, R*S <= 64, operands < 2 GiB), 0 per-lane global loads. */
 int mx_conv_set_loader(int loader);
@@ -394,8 +412,7 @@ int mx_conv_set_stages(int stages);
 /* K-tile order of the buffer-descriptor conv kernels: 0 tap-major, 1 (default) channel-major (all taps
    of a 32-channel chunk before the next chunk: cross-tap re-reads of the gathered rows hit L2). */
 int mx_conv_set_korder(int order);
-/* Timing experiments only: 1 = the bf16x3 buffer kernels skip their epilogue (outputs undefined). */
-int mx_conv_set_debug(int v);
+/* wgrad grid sizing: the pixel axis is split until ~blocks workgroups (0 = one wave of resident blocks). */
 int mx_conv_set_wgrad_target(int64_t blocks);
 /* The calling thread's last conv launch (fwd / dgrad / wgrad, bf16 and bf16x3 entries), for tests that
  * assert which path a shape took: out[0] pass (0 fwd, 1 dgrad, 2 wgrad), out[1] x out[2] block tile
@@ -420,9 +437,10 @@ int mx_conv_last_launch(int32_t out[8]);
  *   dgrad_x3: part != NULL adds the mx_conv2d_dgrad_bnb BN-backward partials (y, z, mean, invstd, act
  *   of the BN whose output gradient dx is; stride 1), else those arguments are ignored.
  * ------------------------------------------------------------------------------------------- */
-size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass);
+size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg);
 int mx_conv2d_fwd_x3(const mx_conv_shape* s, const float* x, const uint16_t* w, const float* bias, const float* residual,
-                     int act, float* y, float* stats, void* ws, size_t ws_bytes, mx_stream_t stream);
+                     int act, float* y, float* stats, void* ws, size_t ws_bytes, mx_stream_t stream,
+                     const mx_conv_cfg* cfg);
 /* The ResNet stem as mx_conv2d_fwd_x3 (torchvision resnet50 conv1, reached from
  * train_frcnn_baseline.py:171 through the detector's backbone): R = S = 7, K = 64, the same packed w
  * [2][64][7][7][C] and outputs (y = act(conv + bias), optional BN statistics partials, no residual),
@@ -432,9 +450,9 @@ int mx_conv2d_stem_x3(const mx_conv_shape* s, const float* x, const uint16_t* w,
                       float* stats, mx_stream_t stream);
 int mx_conv2d_dgrad_x3(const mx_conv_shape* s, const float* dy, const uint16_t* wt, const float* residual, float* dx,
                        const float* y, const float* z, const float* mean, const float* invstd, int act, float* part,
-                       int64_t part_mb, void* ws, size_t ws_bytes, mx_stream_t stream);
+                       int64_t part_mb, void* ws, size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg);
 int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const float* x, float* dw, int64_t Kout, int64_t Cin,
-                       int layout, void* ws, size_t ws_bytes, mx_stream_t stream);
+                       int layout, void* ws, size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg);
 
 /* NHWC pooling / resampling (dtype MX_BF16 or MX_F32 storage, C % 8 == 0).
  * maxpool: F.max_pool2d (ResNet stem k3 s2 p1 — torchvision resnet50 reached at

@@ -64,7 +64,6 @@ struct ConvP {
   // block gathers between two visits of the same cache line shrink from BMT full pixel rows to the
   // tap window of one chunk, so the re-reads across taps stay in L2
   int korder;
-  int dbg_skip_epi;  // timing experiments only (mx_conv_set_debug): skip the bf16x3 buffer kernel's epilogue
   // dgrad feeding a train-mode BatchNorm backward (mx_conv2d_dgrad_bnb): per 64-row block column
   // sums of g = bf16(dx) * act'(y) and g * (z - mean) * invstd -> bnb_part [2][mblocks64][Ncol]
   const void* bnb_y;
@@ -1767,7 +1766,7 @@ __global__ void __launch_bounds__(64 * WR * WC, OCC) conv_x3_buf_kernel(ConvP p)
   const int korder = __builtin_amdgcn_readfirstlane(p.korder);
   KPos kp;
   kp.init(korder, (int)kbeg, R, S, IC, 32);
-  // timing-only diagnostics (round 2, mx_conv_set_debug bits 1 no epilogue, 2 no hi/lo split, 4 no B
+  // timing-only diagnostics (round 2; bits 1 no epilogue, 2 no hi/lo split, 4 no B
   // LDS-DMA, 8 no A LDS-DMA) are compiled out: their run-time tests cost branches and register moves
   // in every K-tile
   constexpr int dbg = 0;
@@ -2933,9 +2932,108 @@ static int conv_check(const mx_conv_shape* s) {
 // rows of the BatchNorm statistics partials (64 output pixels each)
 extern "C" int64_t mx_conv_mblocks(const mx_conv_shape* s) { return cdiv(s->N * s->Ho * s->Wo, SROWS); }
 
-// Kernel variant (mx_conv_set_variant): 0 register staging, 1/2 direct-to-LDS 2-stage (2 also
-// direct-to-LDS wgrad), 3..6 multi-stage direct-to-LDS, 7 (default) per-launch choice of 3 / 4.
-static int g_conv_variant = 7;
+// Launch settings. Every extern "C" entry resolves them once (resolve_cfg): the process defaults
+// g_cfg, with the six per-call values `k` replaced by the caller's mx_conv_cfg when it passes one.
+// Everything below the entries takes the resolved `const Cfg&`; only the mx_conv_set_* / mx_conv_get_*
+// functions and resolve_cfg touch g_cfg.
+struct Cfg {
+  // tile_rows x tile_cols: block-tile override (0 = automatic); max_splits: split-K cap (0 = automatic,
+  // 1 = never split K); stages: LDS ring depth of the 64x128 / 128x128 buffer kernels, the ring /
+  // wave-tile alternative of the bf16x3 ones; wgrad_variant: 0 register-staged 32-pixel K-tiles,
+  // 1 64-pixel K-tiles, 2 direct-to-LDS, 3 (default) buffer descriptors (conv_wgrad_buf_kernel; maps
+  // under 32 output pixels take 0), 4 / 5 bf16x3 128x256 / 256x256 blocks; wgrad_target: blocks the
+  // pixel axis is split towards (0: one full wave of resident blocks, occupancy x CUs)
+  mx_conv_cfg k;
+  // whole-process A/B diagnostics (no per-call form).
+  // variant: 0 register staging, 1/2 direct-to-LDS 2-stage (2 also direct-to-LDS wgrad), 3..6
+  // multi-stage direct-to-LDS, 7 (default) per-launch choice of 3 / 4
+  int variant;
+  // loader: 1 (default) buffer descriptors with wave-uniform tap offsets where the shape allows
+  // (conv_igemm_buf_kernel), 0 the per-lane 64-bit global_load_lds kernels only; 2 / 3 timing-only
+  // (wrong results): the A / B descriptor gets zero records, so the range check drops that operand's
+  // loads (prices its memory traffic)
+  int loader;
+  int korder;  // K-tile order of the buffer kernels (ConvP::korder)
+};
+static Cfg g_cfg = {{0, 0, 0, 0, 3, 0, 0}, 7, 1, 1};
+
+// the one range check of the six per-call values: the setters and every entry that takes a cfg
+static int check_cfg(const mx_conv_cfg& k) {
+  const int r = k.tile_rows, c = k.tile_cols;
+  MX_CHECK_ARG((r == 0 && c == 0) || ((r == 64 || r == 128 || r == 256) && (c == 64 || c == 128 || c == 256)),
+               "conv cfg: tile_rows x tile_cols (mx_conv_set_tile) (0,0) auto, or rows 64/128/256 (256: bf16x3 "
+               "kernels only) x columns 64/128/256");
+  MX_CHECK_ARG(k.max_splits >= 0 && k.max_splits <= 16, "conv cfg: max_splits (mx_conv_set_max_splits) 0 (auto) .. 16");
+  MX_CHECK_ARG(k.stages == 0 || (k.stages >= 3 && k.stages <= 6),
+               "conv cfg: stages (mx_conv_set_stages) 0 (auto), 3, 4, 5 or 6 (x3 kernels: 3 alternative ring, "
+               "4 2x2 wave tiles, 5 alternative ring with wide wave tiles)");
+  MX_CHECK_ARG(k.wgrad_variant >= 0 && k.wgrad_variant <= 5,
+               "conv cfg: wgrad_variant (mx_conv_set_wgrad_variant) 0 px32, 1 px64, 2 direct-to-LDS, 3 buffer "
+               "descriptors, 4 = 3 for bf16 / the 128 x 256 wide block for bf16x3, 5 = 3 / the 256 x 256 block");
+  MX_CHECK_ARG(k.reserved == 0, "conv cfg: reserved must be 0");
+  MX_CHECK_ARG(k.wgrad_target >= 0 && k.wgrad_target <= (1 << 20),
+               "conv cfg: wgrad_target (mx_conv_set_wgrad_target) bad block count (0 = auto)");
+  return MX_OK;
+}
+static int resolve_cfg(const mx_conv_cfg* cfg, Cfg& cf) {
+  cf = g_cfg;
+  if (cfg) {
+    int rc = check_cfg(*cfg);
+    if (rc) return rc;
+    cf.k = *cfg;
+  }
+  return MX_OK;
+}
+static int set_defaults(const mx_conv_cfg& k) {
+  int rc = check_cfg(k);
+  if (!rc) g_cfg.k = k;
+  return rc;
+}
+extern "C" int mx_conv_set_tile(int bmt, int bn) {
+  mx_conv_cfg k = g_cfg.k;
+  k.tile_rows = bmt; k.tile_cols = bn;
+  return set_defaults(k);
+}
+extern "C" int mx_conv_set_max_splits(int n) {
+  mx_conv_cfg k = g_cfg.k;
+  k.max_splits = n;
+  return set_defaults(k);
+}
+extern "C" int mx_conv_set_stages(int n) {
+  mx_conv_cfg k = g_cfg.k;
+  k.stages = n;
+  return set_defaults(k);
+}
+extern "C" int mx_conv_set_wgrad_variant(int v) {
+  mx_conv_cfg k = g_cfg.k;
+  k.wgrad_variant = v;
+  return set_defaults(k);
+}
+extern "C" int mx_conv_set_wgrad_target(int64_t blocks) {
+  mx_conv_cfg k = g_cfg.k;
+  k.wgrad_target = blocks;
+  return set_defaults(k);
+}
+extern "C" int mx_conv_get_wgrad_variant(void) { return g_cfg.k.wgrad_variant; }
+extern "C" int mx_conv_set_variant(int v) {
+  MX_CHECK_ARG(v >= 0 && v <= 9,
+               "mx_conv_set_variant: 0 register staging, 1/2 direct-to-LDS fwd/dgrad, 3-6 multi-stage "
+               "direct-to-LDS (3: BK32x3, 4: BK64x2, 5: BK32x4, 6: BK64x3), 7 auto, 8 64-row tiles BK32x3, "
+               "9 as 7 with 128x256 tiles wherever Ncol >= 256");
+  g_cfg.variant = v;
+  return MX_OK;
+}
+extern "C" int mx_conv_get_variant(void) { return g_cfg.variant; }
+extern "C" int mx_conv_set_loader(int v) {
+  MX_CHECK_ARG(v >= 0 && v <= 3, "mx_conv_set_loader: 0 global_load_lds, 1 buffer descriptors, 2/3 timing-only");
+  g_cfg.loader = v;
+  return MX_OK;
+}
+extern "C" int mx_conv_set_korder(int v) {
+  MX_CHECK_ARG(v == 0 || v == 1, "mx_conv_set_korder: 0 tap-major, 1 channel-major");
+  g_cfg.korder = v;
+  return MX_OK;
+}
 
 // The last conv launch of the calling thread (mx_conv_last_launch): written by launch_igemm,
 // launch_igemm_x3 and the two wgrad entries, so a test can assert the path a shape really took.
@@ -2966,53 +3064,18 @@ struct Geo {
   bool narrow;
 };
 static int num_cus();
-static int g_force_bmt = 0, g_force_bn = 0;  // mx_conv_set_tile (0 = automatic)
-extern "C" int mx_conv_set_tile(int bmt, int bn) {
-  MX_CHECK_ARG((bmt == 0 && bn == 0) || ((bmt == 64 || bmt == 128 || bmt == 256) && (bn == 64 || bn == 128 || bn == 256)),
-               "mx_conv_set_tile: (0,0) auto, or bmt 64/128/256 (256: bf16x3 kernels only) x bn 64/128/256");
-  g_force_bmt = bmt;
-  g_force_bn = bn;
-  return MX_OK;
-}
 
-static int g_buf_stages = 0;  // mx_conv_set_stages: LDS ring depth of the 64x128 / 128x128 buffer kernels
-extern "C" int mx_conv_set_stages(int n) {
-  MX_CHECK_ARG(n == 0 || n == 3 || n == 4 || n == 5 || n == 6,
-               "mx_conv_set_stages: 0 (auto), 3, 4, 5 or 6 (x3 kernels: 3 alternative ring, 4 2x2 wave tiles, "
-               "5 alternative ring with wide wave tiles)");
-  g_buf_stages = n;
-  return MX_OK;
-}
-static int g_conv_debug = 0;  // mx_conv_set_debug: bf16x3 buffer kernel timing-only bits (see the kernel)
-extern "C" int mx_conv_set_debug(int v) {
-  MX_CHECK_ARG(v == 0, "mx_conv_set_debug: the timing-only kernel bits are compiled out (0 only)");
-  g_conv_debug = v;
-  return MX_OK;
-}
-static int g_conv_korder = 1;  // mx_conv_set_korder: K-tile order of the buffer kernels (ConvP::korder)
-extern "C" int mx_conv_set_korder(int v) {
-  MX_CHECK_ARG(v == 0 || v == 1, "mx_conv_set_korder: 0 tap-major, 1 channel-major");
-  g_conv_korder = v;
-  return MX_OK;
-}
-static int g_max_splits = 0;  // mx_conv_set_max_splits (0 = automatic, 1 = never split K)
-extern "C" int mx_conv_set_max_splits(int n) {
-  MX_CHECK_ARG(n >= 0 && n <= 16, "mx_conv_set_max_splits: 0 (auto) .. 16");
-  g_max_splits = n;
-  return MX_OK;
-}
-
-static Geo make_geo(int64_t M, int64_t Ncol, int64_t Kdim) {
+static Geo make_geo(const Cfg& cf, int64_t M, int64_t Ncol, int64_t Kdim) {
   Geo g;
   g.M = M; g.Ncol = Ncol; g.Kdim = Kdim;
   g.narrow = g.Ncol <= 64;
   g.bn = g.narrow ? 64 : 128;
   g.bmt = BM;
   g.tiles = cdiv(g.M, BM) * cdiv(g.Ncol, g.bn);
-  if (g_conv_variant == 9 && g.Ncol >= 256) {
+  if (cf.variant == 9 && g.Ncol >= 256) {
     g.bn = 256;
     g.tiles = cdiv(g.M, BM) * cdiv(g.Ncol, 256);
-  } else if (g_conv_variant == 7 && !g.narrow && g.tiles >= 320) {
+  } else if (cf.variant == 7 && !g.narrow && g.tiles >= 320) {
     // big grids: pick the block tile by (relative per-round throughput) x (wave fill), where a
     // round is one resident block per slot (occupancy x CUs): 128x256 reads the gathered A operand
     // once per 256 output channels and issues 12 LDS reads per 32 MFMAs (fastest per full round),
@@ -3034,34 +3097,34 @@ static Geo make_geo(int64_t M, int64_t Ncol, int64_t Kdim) {
   }
   const int64_t ntn = cdiv(g.Ncol, g.bn);
   // small grids: 64-row tiles first (twice the blocks, no partial-sum traffic), split-K only below that
-  if (g.bn != 256 && g.bmt == BM && (g_conv_variant == 8 || (g_conv_variant == 7 && g.tiles < 320))) {
+  if (g.bn != 256 && g.bmt == BM && (cf.variant == 8 || (cf.variant == 7 && g.tiles < 320))) {
     g.bmt = 64;
     g.tiles = cdiv(g.M, 64) * ntn;
   }
-  if (g_force_bmt) {
-    g.bmt = std::min(g_force_bmt, 128);
-    g.bn = g_force_bn;
+  if (cf.k.tile_rows) {
+    g.bmt = std::min(cf.k.tile_rows, 128);
+    g.bn = cf.k.tile_cols;
     g.narrow = g.bn == 64;
     g.tiles = cdiv(g.M, g.bmt) * cdiv(g.Ncol, g.bn);
   }
   g.nk = cdiv(g.Kdim, BK);
   g.splits = 1;
   const int64_t split_below = 320;
-  if (g_conv_variant >= 1 && g.Ncol % 8 == 0 && g.tiles < split_below && g.nk >= 8) {
+  if (cf.variant >= 1 && g.Ncol % 8 == 0 && g.tiles < split_below && g.nk >= 8) {
     int64_t sp = std::min<int64_t>(std::min<int64_t>(cdiv(640, g.tiles), g.nk / 4), 16);
     g.splits = (int)std::max<int64_t>(1, sp);
   }
-  if (g_max_splits && g.splits > g_max_splits) g.splits = g_max_splits;
+  if (cf.k.max_splits && g.splits > cf.k.max_splits) g.splits = cf.k.max_splits;
   return g;
 }
 
 // The variant a launch runs: long K loops on big grids favour 64-wide K-tiles (fewer barriers),
 // short loops and small / split grids the 3-deep 32-wide ring at 3 blocks per CU; 64-row tiles
 // for grids under ~1.25 blocks per CU.
-static int launch_kind(const Geo& g) {
+static int launch_kind(const Cfg& cf, const Geo& g) {
   if (g.bn == 256 && g.bmt == 128) return 9;
   if (g.bmt == 64) return 8;
-  if (g_conv_variant != 7) return g_conv_variant;
+  if (cf.variant != 7) return cf.variant;
   if (g.splits > 1 || g.nk < 16) return 3;
   // wave quantisation: BK32x3 holds 3 blocks per CU, BK64x2 holds 2 (each then ~1.5x faster)
   const int64_t cus = num_cus();
@@ -3108,13 +3171,14 @@ static int dgrad_classes(const mx_conv_shape* s, int64_t Cpad, int64_t Kpad, DCl
   return n;
 }
 
-static size_t wgrad_ws(const mx_conv_shape* s);
+static size_t wgrad_ws(const Cfg& cf, const mx_conv_shape* s);
 
-extern "C" size_t mx_conv_workspace(const mx_conv_shape* s, int pass) {
-  if (!s || pass < 0 || pass > 2) return 0;
-  if (pass == 2) return wgrad_ws(s);
+extern "C" size_t mx_conv_workspace(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  if (!s || pass < 0 || pass > 2 || resolve_cfg(cfg, cf)) return 0;
+  if (pass == 2) return wgrad_ws(cf, s);
   if (pass == 0) {
-    Geo g = make_geo(s->N * s->Ho * s->Wo, s->K, s->R * s->S * s->C);
+    Geo g = make_geo(cf, s->N * s->Ho * s->Wo, s->K, s->R * s->S * s->C);
     return g.splits > 1 ? sizeof(float) * (size_t)g.splits * g.M * g.Ncol : 0;
   }
   if (s->stride_h < 1 || s->stride_h > 2 || s->stride_w < 1 || s->stride_w > 2) return 0;
@@ -3125,7 +3189,7 @@ extern "C" size_t mx_conv_workspace(const mx_conv_shape* s, int pass) {
   size_t mx = 0;
   for (int i = 0; i < n; ++i) {
     if (cl[i].Hc * cl[i].Wc == 0) continue;  // an empty parity class (H or W of 1) is not launched
-    Geo g = make_geo(s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
+    Geo g = make_geo(cf, s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
     if (g.splits > 1) mx = std::max(mx, sizeof(float) * (size_t)g.splits * g.M * g.Ncol);
   }
   return mx;
@@ -3143,17 +3207,6 @@ static void launch_buf(const ConvP& p, int64_t blocks, hipStream_t st) {
   size_t ring = (size_t)STAGES * (BMT + BN) * 32 * 2;
   size_t epi = (size_t)(BMT / 2) * (BN + 4) * 4;
   conv_igemm_buf_kernel<BN, MODE, STAGES, OCC, BMT><<<(unsigned)blocks, NT, std::max(ring, epi), st>>>(p);
-}
-
-// A/B loader: 1 (default) buffer descriptors with wave-uniform tap offsets where the shape allows
-// (conv_igemm_buf_kernel), 0 the per-lane 64-bit global_load_lds kernels only
-static int g_conv_loader = 1;
-extern "C" int mx_conv_set_loader(int v) {
-  // 2 / 3: timing-only diagnostics (wrong results): the A / B descriptor gets zero records, so the
-  // range check drops that operand's loads (prices its memory traffic)
-  MX_CHECK_ARG(v >= 0 && v <= 3, "mx_conv_set_loader: 0 global_load_lds, 1 buffer descriptors, 2/3 timing-only");
-  g_conv_loader = v;
-  return MX_OK;
 }
 
 template <int BN, int MODE>
@@ -3178,14 +3231,14 @@ static void launch_variant(int v, const ConvP& p, int64_t blocks, hipStream_t st
 }
 
 template <int MODE>
-static int launch_igemm(ConvP& p, const Geo& g, void* ws, size_t ws_bytes, hipStream_t st) {
+static int launch_igemm(const Cfg& cf, ConvP& p, const Geo& g, void* ws, size_t ws_bytes, hipStream_t st) {
   int64_t blocks = g.tiles;
   MX_CHECK_ARG(g.Kdim < (1ll << 30) && p.IH < (1ll << 26) && p.IW < (1ll << 26), "conv: GEMM K or spatial size too large");
   MX_CHECK_ARG(blocks * g.splits < (1ll << 31), "conv: grid too large");
-  const bool buf = g_conv_loader >= 1 && p.IC % 32 == 0 && p.R * p.S <= 64 && p.Kdim % 32 == 0 && p.src_elems > 0 &&
+  const bool buf = cf.loader >= 1 && p.IC % 32 == 0 && p.R * p.S <= 64 && p.Kdim % 32 == 0 && p.src_elems > 0 &&
                    p.src_elems * 2 < (1ll << 31) && p.wt_elems > 0 && p.wt_elems * 2 < (1ll << 31);
   MX_CHECK_ARG(buf || g.bn != 256 || g.bmt == BM, "conv: 64x256 tiles need the buffer loader");
-  const int v = buf ? 3 : launch_kind(g);
+  const int v = buf ? 3 : launch_kind(cf, g);
   const int64_t bkt = (buf || v == 3 || v == 5 || v == 8 || v == 9) ? 32 : 64;
   const int64_t nk = cdiv(g.Kdim, bkt);  // K-tiles in the kernel's tile width
   p.splits = 1;
@@ -3200,19 +3253,19 @@ static int launch_igemm(ConvP& p, const Geo& g, void* ws, size_t ws_bytes, hipSt
     blocks *= p.splits;
   }
   if (buf) {
-    p.korder = g_conv_korder;
-    if (g_conv_loader == 2) p.src_elems = 0;
-    if (g_conv_loader == 3) p.wt_elems = 0;
+    p.korder = cf.korder;
+    if (cf.loader == 2) p.src_elems = 0;
+    if (cf.loader == 3) p.wt_elems = 0;
     if (g.bmt == 64) {
       if (g.bn == 256) launch_buf<256, MODE, 3, 2, 64>(p, blocks, st);
       else if (g.narrow) launch_buf<64, MODE, 3, 4, 64>(p, blocks, st);
-      else if (g_buf_stages == 4) launch_buf<128, MODE, 4, 3, 64>(p, blocks, st);
-      else if (g_buf_stages == 6) launch_buf<128, MODE, 6, 2, 64>(p, blocks, st);
+      else if (cf.k.stages == 4) launch_buf<128, MODE, 4, 3, 64>(p, blocks, st);
+      else if (cf.k.stages == 6) launch_buf<128, MODE, 6, 2, 64>(p, blocks, st);
       else launch_buf<128, MODE, 3, 4, 64>(p, blocks, st);
     } else if (g.bn == 256) launch_buf<256, MODE, 3, 2, 128>(p, blocks, st);
     else if (g.narrow) launch_buf<64, MODE, 3, 3, 128>(p, blocks, st);
-    else if (g_buf_stages == 4) launch_buf<128, MODE, 4, 2, 128>(p, blocks, st);
-    else if (g_buf_stages == 6) launch_buf<128, MODE, 6, 1, 128>(p, blocks, st);
+    else if (cf.k.stages == 4) launch_buf<128, MODE, 4, 2, 128>(p, blocks, st);
+    else if (cf.k.stages == 6) launch_buf<128, MODE, 6, 1, 128>(p, blocks, st);
     else launch_buf<128, MODE, 3, 3, 128>(p, blocks, st);
   } else if (g.bn == 256) launch_pipe<256, MODE, 32, 3, 2>(p, blocks, st);
   else if (g.narrow) launch_variant<64, MODE>(v, p, blocks, st);
@@ -3233,32 +3286,13 @@ static int launch_igemm(ConvP& p, const Geo& g, void* ws, size_t ws_bytes, hipSt
   return MX_OK;
 }
 
-extern "C" int mx_conv_get_variant(void) { return g_conv_variant; }
-
-// wgrad kernel variant: 0 register-staged 32-pixel K-tiles, 1 64-pixel K-tiles, 2 direct-to-LDS,
-// 3 (default) buffer descriptors (conv_wgrad_buf_kernel; maps under 32 output pixels take 0)
-static int g_wgrad_variant = 3;
-extern "C" int mx_conv_set_wgrad_variant(int v) {
-  MX_CHECK_ARG(v >= 0 && v <= 5, "mx_conv_set_wgrad_variant: 0 px32, 1 px64, 2 direct-to-LDS, 3 buffer descriptors, "
-                                "4 = 3 for bf16 / the 128 x 256 wide block for bf16x3");
-  g_wgrad_variant = v;
-  return MX_OK;
-}
-extern "C" int mx_conv_get_wgrad_variant(void) { return g_wgrad_variant; }
-
-extern "C" int mx_conv_set_variant(int v) {
-  MX_CHECK_ARG(v >= 0 && v <= 9,
-               "mx_conv_set_variant: 0 register staging, 1/2 direct-to-LDS fwd/dgrad, 3-6 multi-stage "
-               "direct-to-LDS (3: BK32x3, 4: BK64x2, 5: BK32x4, 6: BK64x3), 7 auto, 8 64-row tiles BK32x3, "
-               "9 as 7 with 128x256 tiles wherever Ncol >= 256");
-  g_conv_variant = v;
-  return MX_OK;
-}
-
 extern "C" int mx_conv2d_fwd_ex(const mx_conv_shape* s, const uint16_t* x, const uint16_t* w, const float* bias,
                                 const uint16_t* residual, int act, void* y, int ydtype, float* stats, void* ws,
-                                size_t ws_bytes, mx_stream_t stream) {
-  int rc = conv_check(s);
+                                size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  if (rc) return rc;
+  rc = conv_check(s);
   if (rc) return rc;
   MX_CHECK_ARG(s->C % 8 == 0, "conv fwd: C=%lld must be a multiple of 8 (pad the input channels)", (long long)s->C);
   MX_CHECK_ARG(ydtype == MX_BF16 || ydtype == MX_F32, "conv fwd: bad output dtype");
@@ -3272,15 +3306,15 @@ extern "C" int mx_conv2d_fwd_ex(const mx_conv_shape* s, const uint16_t* x, const
   p.stats = stats; p.mblocks = cdiv(p.M, SROWS);
   p.src_elems = s->N * s->H * s->W * s->C; p.wt_elems = p.Ncol * p.Kdim;
   g_launch_count = 0;
-  return launch_igemm<0>(p, make_geo(p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
+  return launch_igemm<0>(cf, p, make_geo(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int mx_conv2d_fwd(const mx_conv_shape* s, const uint16_t* x, const uint16_t* w, const float* bias, void* y,
                              int ydtype, float* stats, mx_stream_t stream) {
-  size_t ws = mx_conv_workspace(s, 0);
+  size_t ws = mx_conv_workspace(s, 0, nullptr);
   void* buf = nullptr;
   if (ws) MX_HIP(hipMallocAsync(&buf, ws, (hipStream_t)stream));
-  int rc = mx_conv2d_fwd_ex(s, x, w, bias, nullptr, 0, y, ydtype, stats, buf, ws, stream);
+  int rc = mx_conv2d_fwd_ex(s, x, w, bias, nullptr, 0, y, ydtype, stats, buf, ws, stream, nullptr);
   if (buf) MX_HIP(hipFreeAsync(buf, (hipStream_t)stream));
   return rc;
 }
@@ -3457,7 +3491,7 @@ extern "C" int mx_sgd_pack_step(const void* plan, const float* const* grads, int
 // [C][R][S][K] transpose of mx_conv_transpose_weight)
 extern "C" int mx_conv2d_dgrad_t(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt, uint16_t* dx,
                                  void* ws, size_t ws_bytes, mx_stream_t stream) {
-  return mx_conv2d_dgrad_ex(s, dy, wt, nullptr, dx, ws, ws_bytes, stream);
+  return mx_conv2d_dgrad_ex(s, dy, wt, nullptr, dx, ws, ws_bytes, stream, nullptr);
 }
 
 struct BnbArgs {
@@ -3468,28 +3502,35 @@ struct BnbArgs {
   int64_t mb;
 };
 
-static int dgrad_impl(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt, const uint16_t* residual,
-                      uint16_t* dx, const BnbArgs* bnb, void* ws, size_t ws_bytes, mx_stream_t stream);
+static int dgrad_impl(const Cfg& cf, const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt,
+                      const uint16_t* residual, uint16_t* dx, const BnbArgs* bnb, void* ws, size_t ws_bytes,
+                      mx_stream_t stream);
 
 extern "C" int mx_conv2d_dgrad_ex(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt,
                                   const uint16_t* residual, uint16_t* dx, void* ws, size_t ws_bytes,
-                                  mx_stream_t stream) {
-  return dgrad_impl(s, dy, wt, residual, dx, nullptr, ws, ws_bytes, stream);
+                                  mx_stream_t stream, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  return rc ? rc : dgrad_impl(cf, s, dy, wt, residual, dx, nullptr, ws, ws_bytes, stream);
 }
 
 extern "C" int mx_conv2d_dgrad_bnb(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt,
                                    const uint16_t* residual, uint16_t* dx, const uint16_t* y, const uint16_t* z,
                                    const float* mean, const float* invstd, int act, float* part, int64_t part_mb,
-                                   void* ws, size_t ws_bytes, mx_stream_t stream) {
+                                   void* ws, size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  if (rc) return rc;
   MX_CHECK_ARG(s && s->stride_h == 1 && s->stride_w == 1, "conv dgrad bnb: stride 1 only");
   MX_CHECK_ARG(y && z && mean && invstd && part && act >= 0 && act <= 2, "conv dgrad bnb: bad BN arguments");
   MX_CHECK_ARG(part_mb == cdiv(s->N * s->H * s->W, 64), "conv dgrad bnb: part rows must be cdiv(N*H*W, 64)");
   BnbArgs b{y, z, mean, invstd, act, part, part_mb};
-  return dgrad_impl(s, dy, wt, residual, dx, &b, ws, ws_bytes, stream);
+  return dgrad_impl(cf, s, dy, wt, residual, dx, &b, ws, ws_bytes, stream);
 }
 
-static int dgrad_impl(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt, const uint16_t* residual,
-                      uint16_t* dx, const BnbArgs* bnb, void* ws, size_t ws_bytes, mx_stream_t stream) {
+static int dgrad_impl(const Cfg& cf, const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt,
+                      const uint16_t* residual, uint16_t* dx, const BnbArgs* bnb, void* ws, size_t ws_bytes,
+                      mx_stream_t stream) {
   // residual: a gradient accumulated in the epilogue; under stride 2 each parity class adds it at the
   // pixels it writes (classes without taps write it alone), so every pixel gets it exactly once
   int rc = conv_check(s);
@@ -3519,7 +3560,7 @@ static int dgrad_impl(const mx_conv_shape* s, const uint16_t* dy, const uint16_t
     p.remap = remap; p.rst_h = s->stride_h; p.rst_w = s->stride_w; p.rph = c.ph; p.rpw = c.pw;
     p.rH = s->H; p.rW = s->W;
     p.src_elems = s->N * s->Ho * s->Wo * s->K; p.wt_elems = p.Ncol * p.Kdim;
-    rc = launch_igemm<1>(p, make_geo(p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
+    rc = launch_igemm<1>(cf, p, make_geo(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
     if (rc) return rc;
   }
   return MX_OK;
@@ -3536,7 +3577,7 @@ extern "C" int mx_conv2d_dgrad(const mx_conv_shape* s, const uint16_t* dy, const
   const int64_t RS = s->R * s->S;
   uint16_t* wt = nullptr;
   size_t bytes = sizeof(uint16_t) * s->K * RS * s->C;
-  size_t wsb = mx_conv_workspace(s, 1);
+  size_t wsb = mx_conv_workspace(s, 1, nullptr);
   void* ws = nullptr;
   MX_HIP(hipMallocAsync((void**)&wt, bytes, st));
   if (wsb) MX_HIP(hipMallocAsync(&ws, wsb, st));
@@ -3558,8 +3599,7 @@ extern "C" int mx_conv2d_dgrad(const mx_conv_shape* s, const uint16_t* dy, const
 }
 
 // wgrad launch geometry: 128x128 (k, col) tiles; the pixel axis is split until the grid covers
-// ~g_wgrad_target blocks (each split's partial goes to a slab, summed by wgrad_reduce_kernel).
-static int64_t g_wgrad_target = 0;  // 0: one full wave of resident blocks (occupancy x CUs)
+// ~wgrad_target blocks (each split's partial goes to a slab, summed by wgrad_reduce_kernel).
 struct WGeo {
   int64_t tiles, splits, kchunk;
   int pxt;
@@ -3575,26 +3615,20 @@ static int num_cus() {
   }
   return g_num_cus;
 }
-static WGeo wgrad_geo(const mx_conv_shape* s) {
+static WGeo wgrad_geo(const Cfg& cf, const mx_conv_shape* s) {
   WGeo g;
   const int64_t P = s->N * s->Ho * s->Wo, Ncol = s->R * s->S * s->C;
   g.tiles = cdiv(s->K, 128) * cdiv(Ncol, 128);
-  const int v = g_wgrad_variant >= 4 ? 3 : g_wgrad_variant;
+  const int v = cf.k.wgrad_variant >= 4 ? 3 : cf.k.wgrad_variant;
   g.pxt = v == 2 ? BKG : (v == 1 ? 64 : BKW);
   // resident blocks per CU: px32 / buffer 3 (142 VGPRs), px64 / direct-to-LDS 2
-  const int64_t slots = g_wgrad_target ? g_wgrad_target : (int64_t)num_cus() * ((v == 0 || v == 3) ? 3 : 2);
+  const int64_t slots = cf.k.wgrad_target ? cf.k.wgrad_target : (int64_t)num_cus() * ((v == 0 || v == 3) ? 3 : 2);
   int64_t splits = std::max<int64_t>(1, slots / g.tiles);  // never past one wave of blocks
   const int64_t max_splits = std::max<int64_t>(1, P / (g.pxt * 4));
   splits = std::min(splits, max_splits);
   g.kchunk = cdiv(cdiv(P, splits), g.pxt) * g.pxt;
   g.splits = cdiv(P, g.kchunk);
   return g;
-}
-
-extern "C" int mx_conv_set_wgrad_target(int64_t blocks) {
-  MX_CHECK_ARG(blocks >= 0 && blocks <= (1 << 20), "mx_conv_set_wgrad_target: bad block count (0 = auto)");
-  g_wgrad_target = blocks;
-  return MX_OK;
 }
 
 // A dense conv (valid RxS on an RxS map: one output pixel per image, FC6 as a 7x7 conv) has the
@@ -3612,18 +3646,21 @@ static mx_conv_shape wgrad_shape(const mx_conv_shape* s, bool* dense) {
   return d;
 }
 
-static size_t wgrad_ws(const mx_conv_shape* s0) {
+static size_t wgrad_ws(const Cfg& cf, const mx_conv_shape* s0) {
   bool dense;
   const mx_conv_shape sd = wgrad_shape(s0, &dense);
   const mx_conv_shape* s = &sd;
-  WGeo g = wgrad_geo(s);
+  WGeo g = wgrad_geo(cf, s);
   return g.splits > 1 ? sizeof(float) * (size_t)g.splits * s->K * s->R * s->S * s->C : 0;
 }
 
 extern "C" int mx_conv2d_wgrad_ex(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* x, float* dw,
                                   int64_t Kout, int64_t Cin, int layout, void* ws, size_t ws_bytes,
-                                  mx_stream_t stream) {
-  int rc = conv_check(s);
+                                  mx_stream_t stream, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  if (rc) return rc;
+  rc = conv_check(s);
   if (rc) return rc;
   MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "conv wgrad: K and C must be multiples of 8");
   MX_CHECK_ARG(Kout >= 1 && Kout <= s->K && Cin >= 1 && Cin <= s->C, "conv wgrad: Kout/Cin out of range");
@@ -3641,7 +3678,7 @@ extern "C" int mx_conv2d_wgrad_ex(const mx_conv_shape* s, const uint16_t* dy, co
   p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
   p.Kout = Kout; p.Cin = Cin; p.layout = layout;
   p.dC = dC; p.dRS = dRS;
-  WGeo g = wgrad_geo(s);
+  WGeo g = wgrad_geo(cf, s);
   p.kchunk = g.kchunk;
   if (g.splits > 1) {
     const size_t need = sizeof(float) * (size_t)g.splits * p.K * p.Ncol;
@@ -3651,7 +3688,7 @@ extern "C" int mx_conv2d_wgrad_ex(const mx_conv_shape* s, const uint16_t* dy, co
   }
   MX_CHECK_ARG(g.tiles < (1ll << 31) && g.splits < 65536, "conv wgrad: grid too large");
   dim3 grid((unsigned)g.tiles, (unsigned)g.splits);
-  int v = g_wgrad_variant >= 4 ? 3 : g_wgrad_variant;
+  int v = cf.k.wgrad_variant >= 4 ? 3 : cf.k.wgrad_variant;
   // the buffer kernel walks each lane's pixels by (n, oh, ow) increments: maps of fewer than 32
   // output pixels (FC6 as a 7x7 conv on the RoI tile) would wrap many times per tile -> register kernel
   if (v == 3 && !(p.P * p.K * 2 < (1ll << 31) && s->N * s->H * s->W * s->C * 2 < (1ll << 31) &&
@@ -3676,10 +3713,10 @@ extern "C" int mx_conv2d_wgrad(const mx_conv_shape* s, const uint16_t* dy, const
   // convenience form: dw [K][R][S][C] f32 (overwritten), temporaries allocated per call
   int rc = conv_check(s);
   if (rc) return rc;
-  size_t wsb = wgrad_ws(s);
+  size_t wsb = mx_conv_workspace(s, 2, nullptr);
   void* ws = nullptr;
   if (wsb) MX_HIP(hipMallocAsync(&ws, wsb, (hipStream_t)stream));
-  rc = mx_conv2d_wgrad_ex(s, dy, x, dw, s->K, s->C, 0, ws, wsb, stream);
+  rc = mx_conv2d_wgrad_ex(s, dy, x, dw, s->K, s->C, 0, ws, wsb, stream, nullptr);
   if (ws) MX_HIP(hipFreeAsync(ws, (hipStream_t)stream));
   return rc;
 }
@@ -3687,7 +3724,7 @@ extern "C" int mx_conv2d_wgrad(const mx_conv_shape* s, const uint16_t* dy, const
 // ================================================================================================
 // bf16x3 (f32 activation) entry points: same GEMM decompositions as the bf16 path (fwd, dgrad per
 // stride-parity class, wgrad split over pixels), f32 activations / gradients, split weights.
-static Geo make_geo_x3(int64_t M, int64_t Ncol, int64_t Kdim) {
+static Geo make_geo_x3(const Cfg& cf, int64_t M, int64_t Ncol, int64_t Kdim) {
   Geo g;
   g.M = M; g.Ncol = Ncol; g.Kdim = Kdim;
   g.narrow = Ncol <= 64;
@@ -3704,9 +3741,9 @@ static Geo make_geo_x3(int64_t M, int64_t Ncol, int64_t Kdim) {
     g.bmt = 64;
     g.tiles = cdiv(M, 64) * cdiv(Ncol, g.bn);
   }
-  if (g_force_bmt) {
-    g.bmt = g_force_bmt;
-    g.bn = g.bmt == 256 ? 128 : std::min(g_force_bn, 128);
+  if (cf.k.tile_rows) {
+    g.bmt = cf.k.tile_rows;
+    g.bn = g.bmt == 256 ? 128 : std::min(cf.k.tile_cols, 128);
     g.narrow = g.bn == 64;
     g.tiles = cdiv(M, g.bmt) * cdiv(Ncol, g.bn);
   }
@@ -3716,7 +3753,7 @@ static Geo make_geo_x3(int64_t M, int64_t Ncol, int64_t Kdim) {
     int64_t sp = std::min<int64_t>(std::min<int64_t>(cdiv(640, g.tiles), g.nk / 4), 16);
     g.splits = (int)std::max<int64_t>(1, sp);
   }
-  if (g_max_splits && g.splits > g_max_splits) g.splits = g_max_splits;
+  if (cf.k.max_splits && g.splits > cf.k.max_splits) g.splits = cf.k.max_splits;
   // the splits the launch fills (equal shares of whole K-tiles): the workspace holds no unused slab
   if (g.splits > 1) g.splits = (int)cdiv(g.nk, cdiv(g.nk, (int64_t)g.splits));
   return g;
@@ -3737,8 +3774,8 @@ static void launch_x3_buf(const ConvP& p, int64_t blocks, hipStream_t st) {
 }
 
 template <int MODE>
-static int launch_igemm_x3(ConvP& p, const Geo& g0, void* ws, size_t ws_bytes, hipStream_t st) {
-  const bool buf = g_conv_loader >= 1 && p.IC % 32 == 0 && p.R * p.S <= 64 && p.Kdim % 32 == 0 && p.src_elems > 0 &&
+static int launch_igemm_x3(const Cfg& cf, ConvP& p, const Geo& g0, void* ws, size_t ws_bytes, hipStream_t st) {
+  const bool buf = cf.loader >= 1 && p.IC % 32 == 0 && p.R * p.S <= 64 && p.Kdim % 32 == 0 && p.src_elems > 0 &&
                    p.src_elems * 4 < (1ll << 31) && p.wt_elems > 0 && p.wt_plane + p.wt_elems < (1ll << 30);
   Geo g = g0;
   if (g.bmt == 256 && !buf) {  // 256-row tiles exist only as the buffer kernel
@@ -3764,15 +3801,14 @@ static int launch_igemm_x3(ConvP& p, const Geo& g0, void* ws, size_t ws_bytes, h
   MX_CHECK_ARG(blocks < (1ll << 31), "conv: grid too large");
   if (buf) {
     // ring depth x blocks per CU; mx_conv_set_stages(3) picks the alternative of each tile shape
-    const bool alt = g_buf_stages == 3;
+    const bool alt = cf.k.stages == 3;
     // 128 x 128 / 64 x 128 tiles as 4 wide wave tiles (32 x 128 / 16 x 128: each A row split by one
     // wave) unless mx_conv_set_stages(4) asks for the 2 x 2 layout of 64 x 64 / 32 x 64 wave tiles
-    const bool wide = g_buf_stages == 0, wide64 = wide;
-    const bool altw = g_buf_stages == 5;  // the alternative ring depth with wide wave tiles
-    p.korder = g_conv_korder;
-    p.dbg_skip_epi = g_conv_debug;
-    if (g_conv_loader == 2) p.src_elems = 0;  // timing-only diagnostics (mx_conv_set_loader)
-    if (g_conv_loader == 3) p.wt_elems = 0;
+    const bool wide = cf.k.stages == 0, wide64 = wide;
+    const bool altw = cf.k.stages == 5;  // the alternative ring depth with wide wave tiles
+    p.korder = cf.korder;
+    if (cf.loader == 2) p.src_elems = 0;  // timing-only diagnostics (mx_conv_set_loader)
+    if (cf.loader == 3) p.wt_elems = 0;
     if (g.bmt == 256) {
       alt ? launch_x3_buf<128, MODE, 2, 1, 256, 4>(p, blocks, st) : launch_x3_buf<128, MODE, 3, 1, 256, 4>(p, blocks, st);
     } else if (g.bmt == 64) {
@@ -3796,7 +3832,7 @@ static int launch_igemm_x3(ConvP& p, const Geo& g0, void* ws, size_t ws_bytes, h
     else launch_x3<128, MODE, 128>(p, blocks, st);
   }
   MX_LAUNCH_CHECK();
-  record_launch(MODE, g.bmt, g.bn, p.splits, g.tiles, buf, 100 + (buf ? g_buf_stages : 0));
+  record_launch(MODE, g.bmt, g.bn, p.splits, g.tiles, buf, 100 + (buf ? cf.k.stages : 0));
   if (p.slab) {
     if (cdiv(g.M, BM) * cdiv(g.Ncol, 64) >= 2 * (int64_t)num_cus()) {
       dim3 rg((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.Ncol, 64));
@@ -3812,16 +3848,16 @@ static int launch_igemm_x3(ConvP& p, const Geo& g0, void* ws, size_t ws_bytes, h
 
 // wgrad x3 block shape: 0 = 128 x 128 (4 waves, 2 blocks per CU), 1 = 128 x 256 (8 waves, one block
 // per CU; mx_conv_set_wgrad_variant(4) -- a tuner candidate)
-static int wgrad_x3_wide() { return g_wgrad_variant == 4; }
+static int wgrad_x3_wide(const Cfg& cf) { return cf.k.wgrad_variant == 4; }
 // 5: 256 x 256 tile, one wave per SIMD (conv_wgrad_x3ww_kernel; a tuner candidate)
-static int wgrad_x3_ww() { return g_wgrad_variant == 5; }
-static WGeo wgrad_geo_x3(const mx_conv_shape* s) {
+static int wgrad_x3_ww(const Cfg& cf) { return cf.k.wgrad_variant == 5; }
+static WGeo wgrad_geo_x3(const Cfg& cf, const mx_conv_shape* s) {
   WGeo g;
   const int64_t P = s->N * s->Ho * s->Wo, Ncol = s->R * s->S * s->C;
-  const bool wide = wgrad_x3_wide(), ww = wgrad_x3_ww();
+  const bool wide = wgrad_x3_wide(cf), ww = wgrad_x3_ww(cf);
   g.tiles = ww ? cdiv(s->K, 256) * cdiv(Ncol, 256) : cdiv(s->K, 128) * cdiv(Ncol, wide ? 256 : 128);
   g.pxt = 32;
-  const int64_t slots = g_wgrad_target ? g_wgrad_target : (int64_t)num_cus() * ((wide || ww) ? 1 : 2);
+  const int64_t slots = cf.k.wgrad_target ? cf.k.wgrad_target : (int64_t)num_cus() * ((wide || ww) ? 1 : 2);
   int64_t splits = std::max<int64_t>(1, slots / g.tiles);
   const int64_t max_splits = std::max<int64_t>(1, P / (g.pxt * 4));
   splits = std::min(splits, max_splits);
@@ -3830,16 +3866,17 @@ static WGeo wgrad_geo_x3(const mx_conv_shape* s) {
   return g;
 }
 
-extern "C" size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass) {
-  if (!s || pass < 0 || pass > 2) return 0;
+extern "C" size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  if (!s || pass < 0 || pass > 2 || resolve_cfg(cfg, cf)) return 0;
   if (pass == 2) {
     bool dense;
     const mx_conv_shape sd = wgrad_shape(s, &dense);
-    const WGeo g = wgrad_geo_x3(&sd);
+    const WGeo g = wgrad_geo_x3(cf, &sd);
     return g.splits > 1 ? sizeof(float) * (size_t)g.splits * sd.K * sd.R * sd.S * sd.C : 0;
   }
   if (pass == 0) {
-    const Geo g = make_geo_x3(s->N * s->Ho * s->Wo, s->K, s->R * s->S * s->C);
+    const Geo g = make_geo_x3(cf, s->N * s->Ho * s->Wo, s->K, s->R * s->S * s->C);
     return g.splits > 1 ? sizeof(float) * (size_t)g.splits * g.M * g.Ncol : 0;
   }
   if (s->stride_h < 1 || s->stride_h > 2 || s->stride_w < 1 || s->stride_w > 2) return 0;
@@ -3850,7 +3887,7 @@ extern "C" size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass) {
   size_t mx = 0;
   for (int i = 0; i < n; ++i) {
     if (cl[i].Hc * cl[i].Wc == 0) continue;  // an empty parity class (H or W of 1) is not launched
-    const Geo g = make_geo_x3(s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
+    const Geo g = make_geo_x3(cf, s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
     if (g.splits > 1) mx = std::max(mx, sizeof(float) * (size_t)g.splits * g.M * g.Ncol);
   }
   return mx;
@@ -3858,8 +3895,11 @@ extern "C" size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass) {
 
 extern "C" int mx_conv2d_fwd_x3(const mx_conv_shape* s, const float* x, const uint16_t* w, const float* bias,
                                 const float* residual, int act, float* y, float* stats, void* ws, size_t ws_bytes,
-                                mx_stream_t stream) {
-  int rc = conv_check(s);
+                                mx_stream_t stream, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  if (rc) return rc;
+  rc = conv_check(s);
   if (rc) return rc;
   MX_CHECK_ARG(s->C % 8 == 0, "conv fwd x3: C=%lld must be a multiple of 8 (pad the input channels)", (long long)s->C);
   MX_CHECK_ARG(s->K % 8 == 0 || !residual, "conv fwd x3: residual needs K %% 8 == 0");
@@ -3873,13 +3913,17 @@ extern "C" int mx_conv2d_fwd_x3(const mx_conv_shape* s, const float* x, const ui
   p.stats = stats; p.mblocks = cdiv(p.M, SROWS);
   p.src_elems = s->N * s->H * s->W * s->C; p.wt_elems = p.Ncol * p.Kdim; p.wt_plane = p.Ncol * p.Kdim;
   g_launch_count = 0;
-  return launch_igemm_x3<0>(p, make_geo_x3(p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
+  return launch_igemm_x3<0>(cf, p, make_geo_x3(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int mx_conv2d_dgrad_x3(const mx_conv_shape* s, const float* dy, const uint16_t* wt, const float* residual,
                                   float* dx, const float* y, const float* z, const float* mean, const float* invstd,
-                                  int act, float* part, int64_t part_mb, void* ws, size_t ws_bytes, mx_stream_t stream) {
-  int rc = conv_check(s);
+                                  int act, float* part, int64_t part_mb, void* ws, size_t ws_bytes, mx_stream_t stream,
+                                  const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  if (rc) return rc;
+  rc = conv_check(s);
   if (rc) return rc;
   MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "conv dgrad x3: K and C must be multiples of 8");
   MX_CHECK_ARG(s->stride_h <= 2 && s->stride_w <= 2, "conv dgrad x3: strides 1 and 2 are supported");
@@ -3912,15 +3956,19 @@ extern "C" int mx_conv2d_dgrad_x3(const mx_conv_shape* s, const float* dy, const
     p.remap = remap; p.rst_h = s->stride_h; p.rst_w = s->stride_w; p.rph = c.ph; p.rpw = c.pw;
     p.rH = s->H; p.rW = s->W;
     p.src_elems = s->N * s->Ho * s->Wo * s->K; p.wt_elems = p.Ncol * p.Kdim;
-    rc = launch_igemm_x3<1>(p, make_geo_x3(p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
+    rc = launch_igemm_x3<1>(cf, p, make_geo_x3(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
     if (rc) return rc;
   }
   return MX_OK;
 }
 
 extern "C" int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const float* x, float* dw, int64_t Kout,
-                                  int64_t Cin, int layout, void* ws, size_t ws_bytes, mx_stream_t stream) {
-  int rc = conv_check(s);
+                                  int64_t Cin, int layout, void* ws, size_t ws_bytes, mx_stream_t stream,
+                                  const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  if (rc) return rc;
+  rc = conv_check(s);
   if (rc) return rc;
   MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "conv wgrad x3: K and C must be multiples of 8");
   MX_CHECK_ARG(Kout >= 1 && Kout <= s->K && Cin >= 1 && Cin <= s->C, "conv wgrad x3: Kout/Cin out of range");
@@ -3938,7 +3986,7 @@ extern "C" int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const
   p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
   p.Kout = Kout; p.Cin = Cin; p.layout = layout;
   p.dC = dC; p.dRS = dRS;
-  const WGeo g = wgrad_geo_x3(s);
+  const WGeo g = wgrad_geo_x3(cf, s);
   p.kchunk = g.kchunk;
   if (g.splits > 1) {
     const size_t need = sizeof(float) * (size_t)g.splits * p.K * p.Ncol;
@@ -3950,16 +3998,16 @@ extern "C" int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const
   MX_CHECK_ARG(p.P * p.K * 4 < (1ll << 31) && p.N * p.H * p.W * p.C * 4 < (1ll << 31) && p.P + 64 < (1ll << 23) &&
                    p.N * p.H * p.W < (1ll << 23) && p.K * 4 < (1ll << 24) && p.C * 4 < (1ll << 24),
                "conv wgrad x3: dy / x must each stay below 2 GiB and 8M pixels (32-bit / 24-bit offset math)");
-  if (wgrad_x3_ww())
+  const bool wide = wgrad_x3_wide(cf), ww = wgrad_x3_ww(cf);
+  if (ww)
     conv_wgrad_x3ww_kernel<<<(unsigned)(g.tiles * g.splits), 256, 2 * 8 * 32 * 256, st>>>(p);
-  else if (wgrad_x3_wide())
+  else if (wide)
     conv_wgrad_x3w_kernel<<<(unsigned)(g.tiles * g.splits), 512, 2 * 6 * 32 * 256, st>>>(p);
   else
     conv_wgrad_x3_kernel<<<(unsigned)(g.tiles * g.splits), NT, 2 * 4 * 32 * 256, st>>>(p);
   MX_LAUNCH_CHECK();
   g_launch_count = 0;
-  record_launch(2, wgrad_x3_ww() ? 256 : 128, (wgrad_x3_ww() || wgrad_x3_wide()) ? 256 : 128, g.splits, g.tiles, true,
-                100 + (wgrad_x3_ww() ? 5 : wgrad_x3_wide() ? 4 : 3));
+  record_launch(2, ww ? 256 : 128, (ww || wide) ? 256 : 128, g.splits, g.tiles, true, 100 + (ww ? 5 : wide ? 4 : 3));
   if (g.splits > 1) {
     MX_CHECK_ARG(Kout < 65536, "conv wgrad x3: too many output channels for the split reduce");
     wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);

@@ -26,6 +26,16 @@ class ConvShape(ctypes.Structure):
                 ("pad_h", ctypes.c_int32), ("pad_w", ctypes.c_int32)]
 
 
+class ConvCfg(ctypes.Structure):
+    """mx_conv_cfg (include/mx_det.h): the launch settings of one conv call; NULL = the process defaults."""
+    _fields_ = [("tile_rows", ctypes.c_int32), ("tile_cols", ctypes.c_int32), ("max_splits", ctypes.c_int32),
+                ("stages", ctypes.c_int32), ("wgrad_variant", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("wgrad_target", c_i64)]
+
+
+c_cfg = ctypes.POINTER(ConvCfg)
+
+
 class JpegInfo(ctypes.Structure):
     """mx_jpeg_info (include/mx_det.h)."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32),
@@ -93,8 +103,8 @@ _SIGS = {
     "mx_conv2d_dgrad": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp]),
     "mx_conv2d_wgrad": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp]),
     "mx_conv2d_fwd_ex": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp,
-                                 c_sz, c_vp]),
-    "mx_conv_workspace": (c_sz, [ctypes.POINTER(ConvShape), c_int]),
+                                 c_sz, c_vp, c_cfg]),
+    "mx_conv_workspace": (c_sz, [ctypes.POINTER(ConvShape), c_int, c_cfg]),
     "mx_conv_set_variant": (c_int, [c_int]),
     "mx_conv_get_variant": (c_int, []),
     "mx_conv_set_loader": (c_int, [c_int]),
@@ -102,7 +112,6 @@ _SIGS = {
     "mx_conv_set_max_splits": (c_int, [c_int]),
     "mx_conv_set_stages": (c_int, [c_int]),
     "mx_conv_set_korder": (c_int, [c_int]),
-    "mx_conv_set_debug": (c_int, [c_int]),
     "mx_jpeg_parse": (c_int, [c_vp, c_i64, c_vp]),
     "mx_jpeg_decode_coefs": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "mx_jpeg_workspace": (c_sz, [c_vp]),
@@ -123,21 +132,21 @@ _SIGS = {
     "mx_conv_set_wgrad_target": (c_int, [c_i64]),
     "mx_conv_last_launch": (c_int, [c_vp]),
     "mx_conv2d_wgrad_ex": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp,
-                                   ctypes.c_size_t, c_vp]),
+                                   ctypes.c_size_t, c_vp, c_cfg]),
     "mx_conv_transpose_weight": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]),
     "mx_conv_pack_weight": (c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_vp]),
     "mx_conv_dgrad_weight_elems": (ctypes.c_size_t, [c_vp, c_i64, c_i64]),
     "mx_conv_pack_plan_bytes": (ctypes.c_size_t, [c_i64]),
     "mx_conv_pack_batched": (c_int, [c_vp, c_i64, c_vp, ctypes.c_size_t, c_int, c_vp]),
     "mx_conv2d_dgrad_bnb": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
-                                    c_vp, c_i64, c_vp, c_sz, c_vp]),
+                                    c_vp, c_i64, c_vp, c_sz, c_vp, c_cfg]),
     "mx_rpn_loss_workspace": (c_sz, [c_i64]),
     "mx_rpn_loss_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_vp, c_vp, c_sz, c_vp]),
     "mx_rpn_loss_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mx_roi_loss_fwd": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_f, c_vp, c_vp, c_sz, c_vp]),
     "mx_roi_loss_bwd": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_f, c_vp, c_vp, c_vp, c_vp]),
     "mx_bn_bwd_finalize": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
-    "mx_conv2d_dgrad_ex": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mx_conv2d_dgrad_ex": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp, c_cfg]),
     "mx_conv2d_dgrad_t": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "mx_maxpool_fwd": (c_int, [c_vp, c_int, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "mx_maxpool_bwd": (c_int, [c_vp, c_int, c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_vp, c_vp]),
@@ -172,14 +181,14 @@ _SIGS = {
     "mx_bn_bwd_reduce_ex": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp,
                                     ctypes.c_size_t, c_vp, c_vp, c_vp]),
     "mx_bn_bwd_apply_ex": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
-    "mx_conv_workspace_x3": (c_sz, [ctypes.POINTER(ConvShape), c_int]),
+    "mx_conv_workspace_x3": (c_sz, [ctypes.POINTER(ConvShape), c_int, c_cfg]),
     "mx_conv2d_stem_x3": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     "mx_conv2d_fwd_x3": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_sz,
-                                 c_vp]),
+                                 c_vp, c_cfg]),
     "mx_conv2d_dgrad_x3": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
-                                   c_vp, c_i64, c_vp, c_sz, c_vp]),
+                                   c_vp, c_i64, c_vp, c_sz, c_vp, c_cfg]),
     "mx_conv2d_wgrad_x3": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_sz,
-                                   c_vp]),
+                                   c_vp, c_cfg]),
     "mx_coco_match": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
                               c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mx_coco_accumulate_workspace": (c_sz, [c_i64]),
@@ -192,6 +201,14 @@ _lib = None
 
 class MxError(RuntimeError):
     pass
+
+
+def _cfg_optional(fn, nargs):
+    """The trailing `const mx_conv_cfg*` of a conv entry may be left out from Python: it is then NULL,
+    the process defaults (callers written before the parameter existed keep working)."""
+    def entry(*a):
+        return fn(*a) if len(a) == nargs else fn(*a, None)
+    return entry
 
 
 def load():
@@ -210,6 +227,8 @@ def load():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
+            if args and args[-1] is c_cfg:
+                setattr(lib, name, _cfg_optional(fn, len(args)))
         _lib = lib
     return _lib
 

@@ -137,29 +137,27 @@ _WG_CANDS = ((3, 0), (3, 512), (3, 1024), (3, 384), (2, 0), (0, 0))  # (wgrad ke
 _FD_CANDS_X3 = ((0, 0, 0, 0), (0, 0, 1, 0), (0, 0, 2, 0), (64, 128, 0, 0), (128, 128, 1, 0), (64, 64, 0, 0),
                 (64, 128, 1, 0), (256, 128, 0, 0), (0, 0, 0, 3), (0, 0, 0, 4), (128, 128, 0, 0),
                 (0, 0, 0, 5), (64, 64, 0, 5))
-if __import__("os").environ.get("MX_X3_ALTW", "1") == "0":  # A/B switch for the newest candidate
+if os.environ.get("MX_X3_ALTW", "1") == "0":  # A/B switch for the newest candidate
     _FD_CANDS_X3 = tuple(c for c in _FD_CANDS_X3 if c[3] != 5)
 _WG_CANDS_X3 = ((3, 0), (3, 256), (3, 768), (3, 1024), (4, 0), (4, 512), (5, 0), (5, 512))
 _tune_cache = {}
 
 
 def _tune_on():
-    import os
     return os.environ.get("MX_CONV_TUNE", "1") != "0"
 
 
-def _apply_fd(cfg):
-    call("mx_conv_set_tile", cfg[0], cfg[1])
-    call("mx_conv_set_max_splits", cfg[2])
-    call("mx_conv_set_stages", cfg[3])
+# A candidate reaches the library as an mx_conv_cfg of that one call: it replaces all six launch
+# settings there and touches no process-wide state (the mx_conv_set_* defaults stay what a tool or
+# test made them). None (MX_CONV_TUNE=0) is passed on as NULL: the process defaults govern.
+def _fd_cfg(c):
+    """ConvCfg of a fwd / dgrad candidate (the wgrad fields at the library's defaults)."""
+    return None if c is None else _lib.ConvCfg(c[0], c[1], c[2], c[3], 3, 0, 0)
 
 
-def _apply_wg(c):
-    call("mx_conv_set_wgrad_variant", int(c[0]))
-    call("mx_conv_set_wgrad_target", int(c[1]))
-
-
-_FD_DEFAULT, _WG_DEFAULT = (0, 0, 0, 0), (3, 0)  # the library's own settings (restored after each launch)
+def _wg_cfg(c):
+    """ConvCfg of a wgrad candidate (the fwd / dgrad fields automatic)."""
+    return None if c is None else _lib.ConvCfg(0, 0, 0, 0, int(c[0]), 0, int(c[1]))
 
 
 _spin = []  # spin-kernel cycles per ms on this device (measured once)
@@ -188,34 +186,31 @@ def _gpu_time(run, reps=3):
     return e0.elapsed_time(e1)
 
 
-def _tuned(key, cands, apply, run, default):
-    """Launch `run` under the cached best candidate for `key` (timing the candidates at first use).
-    MX_CONV_TUNE=0 leaves the library's launch settings untouched (defaults or mx_conv_set_*)."""
-    if not _tune_on():
-        return run()
-    cfg = _tune_cache.get(key)
-    if cfg is None:
+def _pick(key, cands, run):
+    """The cached best candidate for `key`, timing `run(candidate)` for each at first use (under a
+    KernelTimer or a graph capture: cands[0], uncached)."""
+    c = _tune_cache.get(key)
+    if c is None:
         if _timer is not None or torch.cuda.is_current_stream_capturing():
-            cfg = cands[0]
-        else:
-            # two interleaved rounds, each candidate's faster one kept: a single timing per candidate
-            # let clock / cache noise pick different winners from run to run
-            ts = [float("inf")] * len(cands)
-            for _ in range(2):
-                for i, c in enumerate(cands):
-                    apply(c)
-                    ts[i] = min(ts[i], _gpu_time(run))
-            best = None
-            for t, c in zip(ts, cands):
-                if best is None or t < 0.97 * best[0]:  # prefer the earlier (default) within 3 %
-                    best = (t, c)
-            cfg = best[1]
-            _tune_cache[key] = cfg
-    apply(cfg)
-    try:
-        return run()
-    finally:
-        apply(default)
+            return cands[0]
+        # two interleaved rounds, each candidate's faster one kept: a single timing per candidate
+        # let clock / cache noise pick different winners from run to run
+        ts = [float("inf")] * len(cands)
+        for _ in range(2):
+            for i, c in enumerate(cands):
+                ts[i] = min(ts[i], _gpu_time(lambda: run(c)))
+        best = None
+        for t, c in zip(ts, cands):
+            if best is None or t < 0.97 * best[0]:  # prefer the earlier (default) within 3 %
+                best = (t, c)
+        c = _tune_cache[key] = best[1]
+    return c
+
+
+def _tuned(key, cands, run):
+    """run(candidate) under the cached best candidate for `key` (_pick). MX_CONV_TUNE=0: run(None),
+    the library's process defaults (its own, or what mx_conv_set_* installed)."""
+    return run(_pick(key, cands, run) if _tune_on() else None)
 
 
 def conv_fwd(x, wk, stride, pad, bias=None, residual=None, act=ACT_NONE, out_dtype=None, stats=False, cin=None):
@@ -253,20 +248,21 @@ def conv_fwd(x, wk, stride, pad, bias=None, residual=None, act=ACT_NONE, out_dty
                         x.numel() * x.element_size() + wk.numel() * 2 + y.numel() * y.element_size())
         return (y, st) if stats else y
 
-    def run():
+    def run(c):
+        cfg = _fd_cfg(c)  # the one object sizes the workspace and launches
         if x3:
-            wsb = _lib.load().mx_conv_workspace_x3(ctypes.byref(sh), 0)
+            wsb = _lib.load().mx_conv_workspace_x3(ctypes.byref(sh), 0, cfg)
             ws = torch.empty(wsb, dtype=torch.uint8, device=x.device) if wsb else None
             call("mx_conv2d_fwd_x3", ctypes.byref(sh), _p(x), _p(wk), _p(bias), _p(residual), int(act), _p(y), _p(st),
-                 _p(ws), wsb, _s())
+                 _p(ws), wsb, _s(), cfg)
             return
-        wsb = _lib.load().mx_conv_workspace(ctypes.byref(sh), 0)
+        wsb = _lib.load().mx_conv_workspace(ctypes.byref(sh), 0, cfg)
         ws = torch.empty(wsb, dtype=torch.uint8, device=x.device) if wsb else None
         call("mx_conv2d_fwd_ex", ctypes.byref(sh), _p(x), _p(wk), _p(bias), _p(residual), int(act), _p(y),
-             1 if out_dtype == torch.bfloat16 else 0, _p(st), _p(ws), wsb, _s())
+             1 if out_dtype == torch.bfloat16 else 0, _p(st), _p(ws), wsb, _s(), cfg)
 
     key = ("fwd", x.dtype, sh.N, sh.H, sh.W, C, K, R, S, tuple(stride), tuple(pad), residual is not None, out_dtype)
-    _tuned(key, _FD_CANDS_X3 if x3 else _FD_CANDS, _apply_fd, run, _FD_DEFAULT)
+    _tuned(key, _FD_CANDS_X3 if x3 else _FD_CANDS, run)
     if _timer:
         kind = ("x3_" if x3 else "") + ("fwd128" if K > 64 else "fwd64")
         _timer.stop(kind, 2.0 * sh.N * sh.Ho * sh.Wo * K * R * S * C, t0, _tag(sh.N, sh.H, sh.W, C, K, R, S, stride),
@@ -462,25 +458,26 @@ def conv_dgrad(dy, wt, x_shape, R, S, stride, pad, residual=None, bnb=None):
     if bnb is not None:  # dx is the gradient of a train-mode BN output: its backward partials too
         part = torch.empty((2, mb, C), dtype=torch.float32, device=dy.device)
 
-    def run():
+    def run(c):
+        cfg = _fd_cfg(c)
         if x3:
-            wsb = _lib.load().mx_conv_workspace_x3(ctypes.byref(sh), 1)
+            wsb = _lib.load().mx_conv_workspace_x3(ctypes.byref(sh), 1, cfg)
             ws = torch.empty(wsb, dtype=torch.uint8, device=dy.device) if wsb else None
             b = bnb if part is not None else None
             call("mx_conv2d_dgrad_x3", ctypes.byref(sh), _p(dyc), _p(wt), _p(residual), _p(dx),
                  _p(b.y) if b else None, _p(b.z) if b else None, _p(b.mean) if b else None,
-                 _p(b.invstd) if b else None, int(b.act) if b else 0, _p(part), mb, _p(ws), wsb, _s())
+                 _p(b.invstd) if b else None, int(b.act) if b else 0, _p(part), mb, _p(ws), wsb, _s(), cfg)
             return
-        wsb = _lib.load().mx_conv_workspace(ctypes.byref(sh), 1)
+        wsb = _lib.load().mx_conv_workspace(ctypes.byref(sh), 1, cfg)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dy.device) if wsb else None
         if part is not None:
             call("mx_conv2d_dgrad_bnb", ctypes.byref(sh), _p(dyc), _p(wt), _p(residual), _p(dx), _p(bnb.y),
-                 _p(bnb.z), _p(bnb.mean), _p(bnb.invstd), int(bnb.act), _p(part), mb, _p(ws), wsb, _s())
+                 _p(bnb.z), _p(bnb.mean), _p(bnb.invstd), int(bnb.act), _p(part), mb, _p(ws), wsb, _s(), cfg)
         else:
-            call("mx_conv2d_dgrad_ex", ctypes.byref(sh), _p(dyc), _p(wt), _p(residual), _p(dx), _p(ws), wsb, _s())
+            call("mx_conv2d_dgrad_ex", ctypes.byref(sh), _p(dyc), _p(wt), _p(residual), _p(dx), _p(ws), wsb, _s(), cfg)
 
     key = ("dgrad", dy.dtype, N, H, W, C, K, R, S, tuple(stride), tuple(pad), residual is not None, part is not None)
-    _tuned(key, _FD_CANDS_X3 if x3 else _FD_CANDS, _apply_fd, run, _FD_DEFAULT)
+    _tuned(key, _FD_CANDS_X3 if x3 else _FD_CANDS, run)
     if part is not None:
         bnb.part = part
     if _timer:
@@ -538,7 +535,6 @@ def side_wgrad_enabled(ctx):
     before the join. A weight shared by several calls (the RPN head over the FPN levels) has its
     gradients summed in autograd's input buffer on the main stream, and an existing .grad is added
     to: both would read dw too early. The use count is dropped by the backward that reads it."""
-    import os
     uses, ctx.uses = ctx.uses, None
     if os.environ.get("MX_SIDE_WGRAD", "1") == "0" or _timer is not None:
         return False
@@ -617,7 +613,8 @@ def _join_side():
 
 class _WgradJob:
     """A weight gradient's launch prepared ahead of time (wgrad_prepare): shape, operands, output and
-    split workspace allocated and the tuner's pick applied, so the launch itself allocates nothing."""
+    split workspace allocated, so the launch itself allocates nothing. cfg: the ConvCfg of the tuner's
+    pick (None: the library's process defaults) that sized the workspace and goes to the launch."""
     __slots__ = ("sh", "x3", "entry", "dw", "dyc", "x", "ws", "wsb", "cfg", "kout", "cin", "K", "R", "S", "stride",
                  "t0")
 
@@ -646,19 +643,15 @@ def wgrad_prepare(dy, x, K, R, S, stride, pad, kout=None, cin=None, out=None):
     j.dyc = dyc = dy.contiguous()
     j.t0 = _timer.start() if _timer else None
     key = ("wgrad", x.dtype, sh.N, sh.H, sh.W, x.shape[3], K, R, S, tuple(stride), tuple(pad))
-    if key not in _tune_cache and _tune_on() and _timer is None and not torch.cuda.is_current_stream_capturing():
-        def trial():  # timed on the current stream; the real launch may go to the side stream
-            wsb_ = getattr(_lib.load(), wsfn)(ctypes.byref(sh), 2)
-            ws_ = torch.empty(wsb_, dtype=torch.uint8, device=x.device) if wsb_ else None
-            call(entry, ctypes.byref(sh), _p(dyc), _p(x), _p(dw), kout, cin, 1, _p(ws_), wsb_, _s())
-        _tuned(key, _WG_CANDS_X3 if x3 else _WG_CANDS, _apply_wg, trial, _WG_DEFAULT)
-    j.cfg = _tune_cache.get(key, _WG_DEFAULT) if _tune_on() else None
-    if j.cfg is not None:
-        _apply_wg(j.cfg)
-    j.wsb = getattr(_lib.load(), wsfn)(ctypes.byref(sh), 2)
+    def trial(c):  # timed on the current stream; the real launch may go to the side stream
+        cfg_ = _wg_cfg(c)
+        wsb_ = getattr(_lib.load(), wsfn)(ctypes.byref(sh), 2, cfg_)
+        ws_ = torch.empty(wsb_, dtype=torch.uint8, device=x.device) if wsb_ else None
+        call(entry, ctypes.byref(sh), _p(dyc), _p(x), _p(dw), kout, cin, 1, _p(ws_), wsb_, _s(), cfg_)
+    # the launch (wgrad_launch) gets the object the workspace is sized with here
+    j.cfg = _wg_cfg(_pick(key, _WG_CANDS_X3 if x3 else _WG_CANDS, trial) if _tune_on() else None)
+    j.wsb = getattr(_lib.load(), wsfn)(ctypes.byref(sh), 2, j.cfg)
     j.ws = torch.empty(j.wsb, dtype=torch.uint8, device=x.device) if j.wsb else None
-    if j.cfg is not None:
-        _apply_wg(_WG_DEFAULT)
     return j
 
 
@@ -674,11 +667,7 @@ def wgrad_launch(j, side=False, fork=None):
         else:
             st.wait_stream(torch.cuda.current_stream())
         stream = st.cuda_stream
-    if j.cfg is not None:
-        _apply_wg(j.cfg)
-    call(j.entry, ctypes.byref(j.sh), _p(j.dyc), _p(j.x), _p(j.dw), j.kout, j.cin, 1, _p(j.ws), j.wsb, stream)
-    if j.cfg is not None:
-        _apply_wg(_WG_DEFAULT)
+    call(j.entry, ctypes.byref(j.sh), _p(j.dyc), _p(j.x), _p(j.dw), j.kout, j.cin, 1, _p(j.ws), j.wsb, stream, j.cfg)
     if side:
         ev = torch.cuda.Event()
         ev.record(st)
