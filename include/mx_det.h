@@ -375,6 +375,33 @@ int mx_sgd_pack_build(const mx_sgd_param* params, int64_t nparams, const mx_pack
                       size_t plan_bytes, int64_t* blocks, size_t* lds_bytes);
 int mx_sgd_pack_step(const void* plan, const float* const* grads, int64_t nparams, int64_t blocks, size_t lds_bytes,
                      float lr, float momentum, float dampening, float weight_decay, int nesterov, mx_stream_t stream);
+/* AdamW step (torch.optim.AdamW semantics, see mx_adamw_step) fused with the per-step conv operand
+ * pack, for the restoration U-Net's loop (train_restoration.py:246 builds AdamW(lr 1e-3, weight_decay
+ * 1e-4), :272 steps it, and the next forward packs the new weights): a parameter with `pack` >= 0 is the
+ * f32 weight packs[pack].w, and its update and its wk / wt layouts (exactly what mx_adamw_step followed
+ * by mx_conv_pack_batched would write: split hi / lo planes, the stride-parity dgrad layout, the dense
+ * flag, zero-padded channels) come out of one pass; the others take plain multi-tensor AdamW blocks
+ * of the same launch. Fused packs take R*S <= 49. One launch serves a whole parameter group that
+ * shares one step number (`step`: the number after this step, >= 1); the hyper-parameters are launch
+ * arguments, so a schedule that changes lr needs no new plan.
+ * mx_adamw_pack_build fills a HOST buffer of mx_adamw_pack_plan_bytes(nparams) (no device calls; the
+ * conventions and tiles of mx_sgd_pack_build) and returns the grid size and dynamic LDS bytes; the
+ * caller copies it to device memory (stream-ordered) and launches mx_adamw_pack_step with it and a
+ * device array of the nparams gradient pointers. */
+typedef struct {
+  float* p;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t n;
+  int32_t pack;     /* index into packs[] or -1 */
+  int32_t reserved; /* 0 */
+} mx_adamw_param;
+size_t mx_adamw_pack_plan_bytes(int64_t nparams);
+int mx_adamw_pack_build(const mx_adamw_param* params, int64_t nparams, const mx_pack_desc* packs, void* host_plan,
+                        size_t plan_bytes, int64_t* blocks, size_t* lds_bytes);
+int mx_adamw_pack_step(const void* plan, const float* const* grads, int64_t nparams, int64_t blocks, size_t lds_bytes,
+                       int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                       mx_stream_t stream);
 /* [K][RS][C] -> [C][RS][K] bf16 (the stride-1 dgrad layout). */
 int mx_conv_transpose_weight(const uint16_t* w, int64_t K, int64_t RS, int64_t C, uint16_t* wt, mx_stream_t stream);
 int mx_conv2d_dgrad_t(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt, uint16_t* dx, void* ws,
@@ -557,6 +584,17 @@ int mx_bn_bwd_apply(const uint16_t* dy, const uint16_t* y, const uint16_t* x, in
 int mx_sgd_step(float* const* params, const float* const* grads, float* const* momentum_bufs,
                 const int64_t* numels, const uint8_t* first, int64_t count, float lr, float momentum,
                 float dampening, float weight_decay, int nesterov, mx_stream_t stream);
+/* Multi-tensor AdamW step (torch.optim.AdamW semantics: decoupled decay, no amsgrad, no maximize; the
+ * reference's AdamW(lr 1e-3, weight_decay 1e-4), train_restoration.py:246, step at :272): for each of
+ * `count` f32 tensors (host arrays of device pointers / element counts), with steps[i] the tensor's step
+ * number AFTER this step (>= 1),
+ *   p *= 1 - lr*wd;  m += (1-beta1) * (g - m);  v = v*beta2 + (1-beta2) * (g*g);
+ *   p -= lr / (1 - beta1^step) * (m / (sqrt(v) / sqrt(1 - beta2^step) + eps))
+ * in this order. The constants are derived in double and rounded to f32 once; every f32 op rounds
+ * once (no contraction), division and square root IEEE-rounded. One launch per 64 tensors. */
+int mx_adamw_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                  const int64_t* numels, const int64_t* steps, int64_t count, double lr, double beta1, double beta2,
+                  double eps, double weight_decay, mx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Restoration pre-pass on device (scripts/restore_testsets.py:53-79, restoration_net.py:44-106).

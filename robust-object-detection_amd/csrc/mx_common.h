@@ -149,6 +149,44 @@ __device__ __forceinline__ float sgd_update(float& p, float g, float& b, bool fi
   return p;
 }
 
+// torch.optim.AdamW's update of one element (decoupled decay, no amsgrad, no maximize; the reference's
+// AdamW(lr 1e-3, weight_decay 1e-4), train_restoration.py:246, step at :272), in torch's op order:
+//   p *= decay;  m += w1 * (g - m);  v = v * b2 + w2 * (g * g);
+//   d = sqrt(v) / bc2_sqrt + eps;  p -= step_size * (m / d)
+// The constants are derived on the host in double (adamw_hyper / adamw_bias below: decay = 1 - lr*wd,
+// w1 = 1 - beta1, b2 = beta2, w2 = 1 - beta2, bc2_sqrt = sqrt(1 - beta2^step), step_size =
+// lr / (1 - beta1^step)) and rounded to f32 once. Every f32 op
+// rounds once: no contraction in here, whatever the flags of the file that inlines it, so
+// adamw_kernel (mx_optim.hip) and the pack-fused adamw_pack_kernel (mx_conv.hip) produce the same
+// bits. Division and square root are the IEEE-rounded ones.
+struct AdamwHyper {
+  float decay, w1, b2, w2, eps;
+};
+__device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, const AdamwHyper& h,
+                                             float step_size, float bc2_sqrt) {
+#pragma clang fp contract(off)
+  const float pd = p * h.decay;
+  const float dm = g - m;
+  const float mn = m + h.w1 * dm;
+  const float g2 = g * g;
+  const float vb = v * h.b2;
+  const float vn = vb + h.w2 * g2;
+  const float d = __fsqrt_rn(vn) / bc2_sqrt + h.eps;
+  const float q = mn / d;
+  p = pd - step_size * q;
+  m = mn;
+  v = vn;
+}
+// Host: the f32 constants of adamw_update from double hyper-parameters, as torch derives them from
+// Python floats (pow as Python's float ** float)
+inline AdamwHyper adamw_hyper(double lr, double beta1, double beta2, double eps, double wd) {
+  return AdamwHyper{(float)(1.0 - lr * wd), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps};
+}
+inline void adamw_bias(double lr, double beta1, double beta2, int64_t step, float& step_size, float& bc2_sqrt) {
+  step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
+  bc2_sqrt = (float)pow(1.0 - pow(beta2, (double)step), 0.5);
+}
+
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 

@@ -2601,6 +2601,55 @@ __device__ __forceinline__ void sgd_plain_block(const SgdJob& J, const float* __
   }
 }
 
+// The wk and wt layouts of one kr x tc x (all taps) tile whose new weights sit in LDS as (hi, lo) bf16
+// pairs (hilo_word), T[row * ldt + channel * RS + tap]; rows / channels past K / C hold 0.
+__device__ __forceinline__ void tile_store_layouts(const PackP& pk, int kr, int tc, int64_t k0, int64_t c0,
+                                                   const uint32_t* T, int ldt) {
+  const int RS = pk.R * pk.S;
+  const int np = pk.split ? 2 : 1;
+  // 2. wk [K][R][S][Cpad]: runs of tc channels per (row, tap), written as channel pairs
+  if (pk.wk) {
+    const int h2 = tc >> 1, per = RS * h2;
+    const float inv_per = 1.f / (float)per, inv_h = 1.f / (float)h2;
+    for (int e = threadIdx.x; e < kr * per; e += 256) {
+      const int row = (int)fdiv((uint32_t)e, (uint32_t)per, inv_per), rem = e - row * per;
+      const int rs = (int)fdiv((uint32_t)rem, (uint32_t)h2, inv_h), c2 = rem - rs * h2;
+      const int64_t k = k0 + row, c = c0 + 2 * c2;
+      if (k >= pk.K || c >= pk.Cpad) continue;
+      const uint32_t* tt = T + row * ldt + 2 * c2 * RS + rs;
+      const uint32_t a = tt[0], a2 = tt[RS];  // Cpad is even: c + 1 < Cpad
+      const int64_t dst = (k * RS + rs) * pk.Cpad + c;
+      for (int pl = 0; pl < np; ++pl)
+        *(uint32_t*)(pk.wk + pl * pk.wk_plane + dst) =
+            pl ? (a >> 16) | (a2 & 0xffff0000u) : (a & 0xffffu) | (a2 << 16);
+    }
+  }
+  // 3. wt (dgrad layout): runs along the output channels, written as output-channel pairs
+  if (pk.wt) {
+    const int kr2 = kr >> 1, per = RS * kr2;
+    const float inv_per = 1.f / (float)per, inv_k = 1.f / (float)kr2;
+    for (int e = threadIdx.x; e < tc * per; e += 256) {
+      const int cc = (int)fdiv((uint32_t)e, (uint32_t)per, inv_per), rem = e - cc * per;
+      const int rs = (int)fdiv((uint32_t)rem, (uint32_t)kr2, inv_k), k2 = rem - rs * kr2;
+      const int64_t k = k0 + 2 * k2, c = c0 + cc;
+      if (k >= pk.Kpad || c >= pk.Cpad) continue;
+      const uint32_t* tt = T + 2 * k2 * ldt + cc * RS + rs;
+      const uint32_t a = tt[0], a2 = tt[ldt];  // Kpad is even: k + 1 < Kpad
+      int64_t dst;
+      if (pk.dense) {
+        dst = ((int64_t)rs * pk.Cpad + c) * pk.Kpad + k;
+      } else {
+        const int r = rs / pk.S, sx = rs - r * pk.S;
+        const int q = (r % pk.st_h) * pk.st_w + (sx % pk.st_w);
+        dst = pk.off[q] + ((c * pk.Rc[q] + r / pk.st_h) * pk.Sc[q] + sx / pk.st_w) * pk.Kpad + k;
+      }
+      for (int pl = 0; pl < np; ++pl)
+        *(uint32_t*)(pk.wt + pl * pk.wt_plane + dst) =
+            pl ? (a >> 16) | (a2 & 0xffff0000u) : (a & 0xffffu) | (a2 << 16);
+    }
+  }
+}
+
 __device__ __forceinline__ void sgd_pack_tile(const SgdJob& J, const float* __restrict__ g, int64_t t,
                                               const SgdHyper& h, uint32_t* T) {
   const PackP& pk = J.pk;
@@ -2654,48 +2703,7 @@ __device__ __forceinline__ void sgd_pack_tile(const SgdJob& J, const float* __re
     }
   }
   __syncthreads();
-  const int np = pk.split ? 2 : 1;
-  // 2. wk [K][R][S][Cpad]: runs of tc channels per (row, tap), written as channel pairs
-  if (pk.wk) {
-    const int h2 = tc >> 1, per = RS * h2;
-    const float inv_per = 1.f / (float)per, inv_h = 1.f / (float)h2;
-    for (int e = threadIdx.x; e < kr * per; e += 256) {
-      const int row = (int)fdiv((uint32_t)e, (uint32_t)per, inv_per), rem = e - row * per;
-      const int rs = (int)fdiv((uint32_t)rem, (uint32_t)h2, inv_h), c2 = rem - rs * h2;
-      const int64_t k = k0 + row, c = c0 + 2 * c2;
-      if (k >= pk.K || c >= pk.Cpad) continue;
-      const uint32_t* tt = T + row * ldt + 2 * c2 * RS + rs;
-      const uint32_t a = tt[0], a2 = tt[RS];  // Cpad is even: c + 1 < Cpad
-      const int64_t dst = (k * RS + rs) * pk.Cpad + c;
-      for (int pl = 0; pl < np; ++pl)
-        *(uint32_t*)(pk.wk + pl * pk.wk_plane + dst) =
-            pl ? (a >> 16) | (a2 & 0xffff0000u) : (a & 0xffffu) | (a2 << 16);
-    }
-  }
-  // 3. wt (dgrad layout): runs along the output channels, written as output-channel pairs
-  if (pk.wt) {
-    const int kr2 = kr >> 1, per = RS * kr2;
-    const float inv_per = 1.f / (float)per, inv_k = 1.f / (float)kr2;
-    for (int e = threadIdx.x; e < tc * per; e += 256) {
-      const int cc = (int)fdiv((uint32_t)e, (uint32_t)per, inv_per), rem = e - cc * per;
-      const int rs = (int)fdiv((uint32_t)rem, (uint32_t)kr2, inv_k), k2 = rem - rs * kr2;
-      const int64_t k = k0 + 2 * k2, c = c0 + cc;
-      if (k >= pk.Kpad || c >= pk.Cpad) continue;
-      const uint32_t* tt = T + 2 * k2 * ldt + cc * RS + rs;
-      const uint32_t a = tt[0], a2 = tt[ldt];  // Kpad is even: k + 1 < Kpad
-      int64_t dst;
-      if (pk.dense) {
-        dst = ((int64_t)rs * pk.Cpad + c) * pk.Kpad + k;
-      } else {
-        const int r = rs / pk.S, sx = rs - r * pk.S;
-        const int q = (r % pk.st_h) * pk.st_w + (sx % pk.st_w);
-        dst = pk.off[q] + ((c * pk.Rc[q] + r / pk.st_h) * pk.Sc[q] + sx / pk.st_w) * pk.Kpad + k;
-      }
-      for (int pl = 0; pl < np; ++pl)
-        *(uint32_t*)(pk.wt + pl * pk.wt_plane + dst) =
-            pl ? (a >> 16) | (a2 & 0xffff0000u) : (a & 0xffffu) | (a2 << 16);
-    }
-  }
+  tile_store_layouts(pk, kr, tc, k0, c0, T, ldt);
 }
 
 // block -> (job, tile or 2048-element chunk) through the prefix sums; grads by job index (their
@@ -2712,6 +2720,128 @@ __global__ void __launch_bounds__(256) sgd_pack_kernel(const SgdJob* __restrict_
   const SgdJob J = jobs[lo];
   if (J.fused) sgd_pack_tile(J, grads[lo], bidx - prefix[lo], h, Tsm);
   else sgd_plain_block(J, grads[lo], bidx - prefix[lo], h);
+}
+
+// ---------------------------------------------------------------------------------------------
+// AdamW step fused with the operand pack (mx_adamw_pack_step): the same tiling as the SGD form above
+// with adamw_update (mx_common.h) as the update -- a block owns a kr x tc x (all taps) tile, updates
+// it in registers (p, exp_avg, exp_avg_sq written back), and writes wk and wt from the (hi, lo) words
+// in LDS. One launch serves a parameter group that shares one step number, so the bias corrections
+// are launch arguments beside the other constants.
+struct AdamwJob {
+  float* p;
+  float* m;
+  float* v;
+  int64_t n;
+  int fused;
+  int kr, tc;
+  int64_t ncb;
+  PackP pk;  // fused: pk.w == p
+};
+struct AdamwStep {
+  AdamwHyper h;
+  float step_size, bc2_sqrt;
+};
+
+__device__ __forceinline__ void adamw_plain_block(const AdamwJob& J, const float* __restrict__ g, int64_t blk,
+                                                  const AdamwStep& s) {
+  const int64_t e0 = blk * SGDP_PER_BLOCK, e1 = min<int64_t>(J.n, e0 + SGDP_PER_BLOCK);
+  float* __restrict__ p = J.p;
+  float* __restrict__ m = J.m;
+  float* __restrict__ v = J.v;
+  if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15u) == 0) {
+    for (int64_t e = e0 + threadIdx.x * 4; e + 3 < e1; e += 256 * 4) {
+      float4 pv = *(float4*)(p + e), mv = *(float4*)(m + e), vv = *(float4*)(v + e);
+      const float4 gv = *(const float4*)(g + e);
+      adamw_update(pv.x, gv.x, mv.x, vv.x, s.h, s.step_size, s.bc2_sqrt);
+      adamw_update(pv.y, gv.y, mv.y, vv.y, s.h, s.step_size, s.bc2_sqrt);
+      adamw_update(pv.z, gv.z, mv.z, vv.z, s.h, s.step_size, s.bc2_sqrt);
+      adamw_update(pv.w, gv.w, mv.w, vv.w, s.h, s.step_size, s.bc2_sqrt);
+      *(float4*)(p + e) = pv;
+      *(float4*)(m + e) = mv;
+      *(float4*)(v + e) = vv;
+    }
+    const int64_t tail = e0 + ((e1 - e0) & ~(int64_t)3);
+    for (int64_t e = tail + threadIdx.x; e < e1; e += 256)
+      adamw_update(p[e], g[e], m[e], v[e], s.h, s.step_size, s.bc2_sqrt);
+  } else {
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256)
+      adamw_update(p[e], g[e], m[e], v[e], s.h, s.step_size, s.bc2_sqrt);
+  }
+}
+
+__device__ __forceinline__ void adamw_pack_tile(const AdamwJob& J, const float* __restrict__ g, int64_t t,
+                                                const AdamwStep& s, uint32_t* T) {
+  const PackP& pk = J.pk;
+  const int RS = pk.R * pk.S;
+  const int kr = J.kr, tc = J.tc;
+  const int64_t k0 = (t / J.ncb) * kr, c0 = (t % J.ncb) * tc;
+  const int width = tc * RS, ldt = width + 1;  // odd row stride: column reads spread over the banks
+  const int64_t cend = pk.C < c0 + tc ? pk.C : c0 + tc;
+  const int nvalid = cend > c0 ? (int)((cend - c0) * RS) : 0;
+  float* __restrict__ p = J.p;
+  float* __restrict__ m = J.m;
+  float* __restrict__ v = J.v;
+  // 1. update the tile: row k's run of nvalid weights starts at (k * C + c0) * RS
+  if ((pk.C & 3) == 0 && ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15u) == 0) {
+    const int w4 = width >> 2, nv4 = nvalid >> 2;
+    const float inv4 = 1.f / (float)w4;
+    for (int e = threadIdx.x; e < kr * w4; e += 256) {
+      const int row = (int)fdiv((uint32_t)e, (uint32_t)w4, inv4), j4 = e - row * w4;
+      const int64_t k = k0 + row;
+      uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
+      if (k < pk.K && j4 < nv4) {
+        const int64_t i = (k * pk.C + c0) * RS + 4 * j4;
+        float4 pv = *(float4*)(p + i), mv = *(float4*)(m + i), vv = *(float4*)(v + i);
+        const float4 gv = *(const float4*)(g + i);
+        adamw_update(pv.x, gv.x, mv.x, vv.x, s.h, s.step_size, s.bc2_sqrt);
+        adamw_update(pv.y, gv.y, mv.y, vv.y, s.h, s.step_size, s.bc2_sqrt);
+        adamw_update(pv.z, gv.z, mv.z, vv.z, s.h, s.step_size, s.bc2_sqrt);
+        adamw_update(pv.w, gv.w, mv.w, vv.w, s.h, s.step_size, s.bc2_sqrt);
+        *(float4*)(p + i) = pv;
+        *(float4*)(m + i) = mv;
+        *(float4*)(v + i) = vv;
+        o0 = hilo_word(pv.x); o1 = hilo_word(pv.y); o2 = hilo_word(pv.z); o3 = hilo_word(pv.w);
+      }
+      uint32_t* d = T + row * ldt + 4 * j4;
+      d[0] = o0; d[1] = o1; d[2] = o2; d[3] = o3;
+    }
+  } else {
+    const float inv = 1.f / (float)width;
+    for (int e = threadIdx.x; e < kr * width; e += 256) {
+      const int row = (int)fdiv((uint32_t)e, (uint32_t)width, inv), j = e - row * width;
+      const int64_t k = k0 + row;
+      uint32_t o = 0;
+      if (k < pk.K && j < nvalid) {
+        const int64_t i = (k * pk.C + c0) * RS + j;
+        float pv = p[i], mv = m[i], vv = v[i];
+        adamw_update(pv, g[i], mv, vv, s.h, s.step_size, s.bc2_sqrt);
+        p[i] = pv;
+        m[i] = mv;
+        v[i] = vv;
+        o = hilo_word(pv);
+      }
+      T[row * ldt + j] = o;
+    }
+  }
+  __syncthreads();
+  tile_store_layouts(pk, kr, tc, k0, c0, T, ldt);
+}
+
+__global__ void __launch_bounds__(256) adamw_pack_kernel(const AdamwJob* __restrict__ jobs,
+                                                         const int64_t* __restrict__ prefix,
+                                                         const float* const* __restrict__ grads, int njobs,
+                                                         AdamwStep s) {
+  extern __shared__ uint32_t Tsm[];
+  const int64_t bidx = blockIdx.x;
+  int lo = 0, hi = njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (prefix[mid] <= bidx) lo = mid; else hi = mid - 1;
+  }
+  const AdamwJob J = jobs[lo];
+  if (J.fused) adamw_pack_tile(J, grads[lo], bidx - prefix[lo], s, Tsm);
+  else adamw_plain_block(J, grads[lo], bidx - prefix[lo], s);
 }
 
 // Host: tile sizes of one pack job (both tile kinds fit PACK_LDS, rows padded by 4 elements)
@@ -3430,6 +3560,28 @@ static bool sgd_tile(int RS, int& kr, int& tc) {
   return false;
 }
 
+// One fused job of mx_sgd_pack_build / mx_adamw_pack_build (`who` in the messages): parameter j (p, n
+// elements) as packs[pack] -> its PackP, tile, channel blocks per row block, block count; lds grows
+// to the tile's (hi, lo) words, rows padded by one
+static int fused_job(const char* who, const mx_pack_desc* packs, int32_t pack, int64_t j, const float* p, int64_t n,
+                     PackP& pk, int& kr, int& tc, int64_t& ncb, int64_t& nb, size_t& lds) {
+  MX_CHECK_ARG(packs, "%s pack build: pack index without pack list", who);
+  const mx_pack_desc& d = packs[pack];
+  int64_t tiles = 0;
+  int rc = make_pack(d, pk, tiles);
+  if (rc) return rc;
+  const int RS = d.R * d.S;
+  MX_CHECK_ARG(d.w == p && d.Kout * d.Cin * RS == n, "%s pack build: pack %lld is not parameter %lld", who,
+               (long long)pack, (long long)j);
+  MX_CHECK_ARG(sgd_tile(RS, kr, tc), "%s pack build: %d taps (fused packing takes <= 49)", who, RS);
+  MX_CHECK_ARG(d.wk || d.wt, "%s pack build: pack %lld has no layout", who, (long long)pack);
+  ncb = cdiv(pk.Cpad, tc);
+  nb = cdiv(pk.Kpad, kr) * ncb;
+  const size_t need = sizeof(uint32_t) * (size_t)kr * (size_t)(tc * RS + 1);
+  if (need > lds) lds = need;
+  return MX_OK;
+}
+
 extern "C" size_t mx_sgd_pack_plan_bytes(int64_t nparams) {
   return nparams > 0 ? sizeof(SgdJob) * (size_t)nparams + sizeof(int64_t) * (size_t)(nparams + 1) : 0;
 }
@@ -3449,21 +3601,9 @@ extern "C" int mx_sgd_pack_build(const mx_sgd_param* params, int64_t nparams, co
     J.p = q.p; J.b = q.buf; J.n = q.n; J.first = q.first ? 1 : 0;
     int64_t nb = cdiv(q.n, SGDP_PER_BLOCK);
     if (q.pack >= 0) {
-      MX_CHECK_ARG(packs, "sgd pack build: pack index without pack list");
-      const mx_pack_desc& d = packs[q.pack];
-      int64_t tiles = 0;
-      int rc = make_pack(d, J.pk, tiles);
+      int rc = fused_job("sgd", packs, q.pack, j, q.p, q.n, J.pk, J.kr, J.tc, J.ncb, nb, lds);
       if (rc) return rc;
-      const int RS = d.R * d.S;
-      MX_CHECK_ARG(d.w == q.p && d.Kout * d.Cin * RS == q.n, "sgd pack build: pack %lld is not parameter %lld",
-                   (long long)q.pack, (long long)j);
-      MX_CHECK_ARG(sgd_tile(RS, J.kr, J.tc), "sgd pack build: %d taps (fused packing takes <= 49)", RS);
-      MX_CHECK_ARG(d.wk || d.wt, "sgd pack build: pack %lld has no layout", (long long)q.pack);
       J.fused = 1;
-      J.ncb = cdiv(J.pk.Cpad, J.tc);
-      nb = cdiv(J.pk.Kpad, J.kr) * J.ncb;
-      const size_t need = sizeof(uint32_t) * (size_t)J.kr * (size_t)(J.tc * RS + 1);
-      if (need > lds) lds = need;
     }
     jobs[j] = J;
     prefix[j + 1] = prefix[j] + nb;
@@ -3483,6 +3623,59 @@ extern "C" int mx_sgd_pack_step(const void* plan, const float* const* grads, int
   const int64_t* prefix = (const int64_t*)((const char*)plan + sizeof(SgdJob) * (size_t)nparams);
   SgdHyper h{lr, momentum, dampening, weight_decay, nesterov};
   sgd_pack_kernel<<<(unsigned)blocks, 256, lds_bytes, (hipStream_t)stream>>>(jobs, prefix, grads, (int)nparams, h);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+extern "C" size_t mx_adamw_pack_plan_bytes(int64_t nparams) {
+  return nparams > 0 ? sizeof(AdamwJob) * (size_t)nparams + sizeof(int64_t) * (size_t)(nparams + 1) : 0;
+}
+
+// the conventions and the tile choice (fused_job, sgd_tile) of mx_sgd_pack_build
+extern "C" int mx_adamw_pack_build(const mx_adamw_param* params, int64_t nparams, const mx_pack_desc* packs,
+                                   void* host_plan, size_t plan_bytes, int64_t* blocks, size_t* lds_bytes) {
+  MX_CHECK_ARG(params && nparams > 0 && nparams < (1 << 20) && blocks && lds_bytes, "adamw pack build: bad lists");
+  MX_CHECK_ARG(host_plan && plan_bytes >= mx_adamw_pack_plan_bytes(nparams), "adamw pack build: plan buffer too small");
+  AdamwJob* jobs = (AdamwJob*)host_plan;
+  int64_t* prefix = (int64_t*)((char*)host_plan + sizeof(AdamwJob) * (size_t)nparams);
+  prefix[0] = 0;
+  size_t lds = 0;
+  for (int64_t j = 0; j < nparams; ++j) {
+    const mx_adamw_param& q = params[j];
+    MX_CHECK_ARG(q.p && q.exp_avg && q.exp_avg_sq && q.n > 0, "adamw pack build: parameter %lld empty or null",
+                 (long long)j);
+    MX_CHECK_ARG(q.reserved == 0, "adamw pack build: parameter %lld has reserved != 0", (long long)j);
+    AdamwJob J{};
+    J.p = q.p; J.m = q.exp_avg; J.v = q.exp_avg_sq; J.n = q.n;
+    int64_t nb = cdiv(q.n, SGDP_PER_BLOCK);
+    if (q.pack >= 0) {
+      int rc = fused_job("adamw", packs, q.pack, j, q.p, q.n, J.pk, J.kr, J.tc, J.ncb, nb, lds);
+      if (rc) return rc;
+      J.fused = 1;
+    }
+    jobs[j] = J;
+    prefix[j + 1] = prefix[j] + nb;
+  }
+  MX_CHECK_ARG(prefix[nparams] < (1ll << 31), "adamw pack build: too many blocks");
+  *blocks = prefix[nparams];
+  *lds_bytes = lds;
+  return MX_OK;
+}
+
+extern "C" int mx_adamw_pack_step(const void* plan, const float* const* grads, int64_t nparams, int64_t blocks,
+                                  size_t lds_bytes, int64_t step, double lr, double beta1, double beta2, double eps,
+                                  double weight_decay, mx_stream_t stream) {
+  MX_CHECK_ARG(plan && grads && nparams > 0 && blocks > 0 && blocks < (1ll << 31) && lds_bytes <= 65536,
+               "adamw pack step: bad plan");
+  MX_CHECK_ARG(step >= 1, "adamw pack step: step %lld (the step number after this step, >= 1)", (long long)step);
+  MX_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adamw pack step: betas outside [0, 1)");
+  MX_CHECK_ARG(eps >= 0.0, "adamw pack step: negative eps");
+  const AdamwJob* jobs = (const AdamwJob*)plan;
+  const int64_t* prefix = (const int64_t*)((const char*)plan + sizeof(AdamwJob) * (size_t)nparams);
+  AdamwStep s{};
+  s.h = adamw_hyper(lr, beta1, beta2, eps, weight_decay);
+  adamw_bias(lr, beta1, beta2, step, s.step_size, s.bc2_sqrt);
+  adamw_pack_kernel<<<(unsigned)blocks, 256, lds_bytes, (hipStream_t)stream>>>(jobs, prefix, grads, (int)nparams, s);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

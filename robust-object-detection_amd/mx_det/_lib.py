@@ -172,6 +172,10 @@ _SIGS = {
     "mx_sgd_pack_plan_bytes": (ctypes.c_size_t, [c_i64]),
     "mx_sgd_pack_build": (c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]),
     "mx_sgd_pack_step": (c_int, [c_vp, c_vp, c_i64, c_i64, ctypes.c_size_t, c_f, c_f, c_f, c_f, c_int, c_vp]),
+    "mx_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_d, c_d, c_d, c_d, c_d, c_vp]),
+    "mx_adamw_pack_plan_bytes": (ctypes.c_size_t, [c_i64]),
+    "mx_adamw_pack_build": (c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.c_size_t, c_vp, c_vp]),
+    "mx_adamw_pack_step": (c_int, [c_vp, c_vp, c_i64, c_i64, ctypes.c_size_t, c_i64, c_d, c_d, c_d, c_d, c_d, c_vp]),
     "mx_bn_apply": (c_int, [c_vp, c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp]),
     "mx_bn_act_maxpool": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp,
                                   c_vp]),

@@ -357,8 +357,9 @@ class WeightPacker:
                         (1 if e.dense else 0) | (2 if e.split else 0))
 
     def fusable(self, params):
-        """Per parameter: the entry whose packing mx_sgd_pack_step can fold into the parameter's SGD
-        update (the parameter's only entry, covering all of it, <= 49 taps), else None."""
+        """Per parameter: the entry whose packing the optimizer can fold into the parameter's update
+        (mx_sgd_pack_step for mx_det.optim.SGD, mx_adamw_pack_step for mx_det.optim.AdamW: the
+        parameter's only entry, covering all of it, <= 49 taps), else None."""
         by_ptr = {}
         for k in self.order:
             e = self.entries[k]
@@ -375,7 +376,8 @@ class WeightPacker:
 
     @staticmethod
     def mark_packed(entries):
-        """The optimizer wrote these entries' operands along with the update (mx_sgd_pack_step)."""
+        """The optimizer wrote these entries' operands along with the update (mx_sgd_pack_step /
+        mx_adamw_pack_step)."""
         for e in entries:
             if e is not None:
                 e.version = e.w._version

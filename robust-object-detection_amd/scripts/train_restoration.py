@@ -6,7 +6,8 @@ L1 + 0.3 (1 - SSIM)), the same data roots, and the same outputs: experiments/res
 best.pth ({"model", "epoch", "psnr", "ssim"}) and last.pth ({"model", "epoch"}), so eval_restored /
 restore_testsets load them unchanged. The U-Net forward/backward runs on the HIP kernels (f32 with
 bf16x3 conv products by default, MX_PRECISION=bf16 for bf16); the corruption of each batch runs on
-the device (mx_det.restoration.RestorationBatcher).
+the device (mx_det.restoration.RestorationBatcher); the optimizer is mx_det.optim.AdamW (one launch
+that also writes the next forward's conv operands; MX_ADAMW=0 for torch.optim.AdamW).
 """
 import json
 import os
@@ -15,6 +16,7 @@ from pathlib import Path
 
 import torch
 
+from mx_det import optim as mx_optim
 from mx_det.engine import init_device, set_seed
 from mx_det.restoration import (CombinedLoss, RestorationBatcher, RestorationDataset, collate_u8, train_epoch,
                                 validate)
@@ -52,7 +54,9 @@ def main(train_dir=TRAIN_IMG_DIR, val_dir=VAL_IMG_DIR, out_dir=OUT_DIR, epochs=E
     print(f"Train: {len(train_ds)} images, Val: {len(val_ds)} images", flush=True)
     model = RestorationUNet(channels=(32, 64, 128, 256)).to(dev)
     print(f"Model parameters: {sum(p.numel() for p in model.parameters()) / 1e6:.2f}M\n", flush=True)
-    optimizer = torch.optim.AdamW(model.parameters(), lr=LR, weight_decay=1e-4)
+    # MX_ADAMW=0: torch.optim.AdamW (foreach kernels, then the packer's repack before the next forward)
+    AdamW = torch.optim.AdamW if os.environ.get("MX_ADAMW", "1") == "0" else mx_optim.AdamW
+    optimizer = AdamW(model.parameters(), lr=LR, weight_decay=1e-4)
     scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)
     criterion = CombinedLoss(ssim_weight=0.3)
     batcher = RestorationBatcher(dev)
