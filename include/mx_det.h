@@ -204,6 +204,44 @@ int mx_box_decode(const float* rel, const float* boxes, int64_t n, int64_t ncls,
                   float clip, float* out, mx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Detection postprocessing for every image of a batch without a host round trip: torchvision
+ * RoIHeads.postprocess_detections (roi_heads.py) + GeneralizedRCNNTransform.postprocess, reached from
+ * eval_all.py:111 / eval_restored.py, model(images) in eval mode. Three stream-ordered steps:
+ *   mx_det_candidates -> mx_batched_nms_grouped(lvl = labels, L = C, group = grp, G = N) -> mx_det_select
+ * ------------------------------------------------------------------------------------------- */
+/* Front half, one launch: softmax, box decode, clip to the image, score and small-box filter.
+ *   logits [R][ldl] f32, C class columns (column 0 = background), 2 <= C <= 1024, ldl >= C;
+ *   reg [R][ldr] f32, 4 values per class, ldr >= 4*C (any strides: rows need no 16-byte alignment);
+ *   rois [R][4] f32 xyxy; img [R] int32 = the image of each row (outside [0, N): a padded / dead row);
+ *   hw [N][2] f32 (h, w) as mx_proposal_clip_filter; weights4_host / clip as mx_box_decode.
+ * For row r and class c in 1..C-1, at the dense index t = r*(C-1) + (c-1) (the order torch's
+ * compaction keeps, so ties broken by index downstream break as in the reference):
+ *   scores[t] = softmax probability in f32: m = max_j x_j; e_j = expf(x_j - m); s = sum of e_j for
+ *     j = 0..C-1 in ascending j; p = e_c / s (IEEE division) -- independent of the launch geometry;
+ *   boxes[t]  = mx_box_decode's box (the same device function) with x clamped to [0, w] and y to [0, h]
+ *     as torch.clamp does (NaN stays NaN, +-inf goes to the bound); a dead row's box is not clamped;
+ *   labels[t] = c (int64);
+ *   grp[t]    = img[r] when the row is live, score > score_thresh (strictly) and the clamped width and
+ *     height are both >= min_size (comparisons false on NaN), else N (dead).
+ * All four outputs are written at every t. R == 0 launches nothing. */
+int mx_det_candidates(const float* logits, int64_t ldl, const float* reg, int64_t ldr, const float* rois,
+                      const int32_t* img, const float* hw, int64_t R, int64_t C, int64_t N,
+                      const float* weights4_host, float clip, float score_thresh, float min_size, float* scores,
+                      float* boxes, int64_t* labels, int32_t* grp, mx_stream_t stream);
+/* Back half, one launch: keep [>= num_keep] / num_keep (device int64) from mx_batched_nms_grouped over
+ * the n = R*(C-1) dense candidates boxes / scores / labels / grp. Per image g < N, with cnt = min(its
+ * number of survivors, D) (D = detections_per_img):
+ *   out_boxes [N][D][4] = its first cnt survivors in keep order (score descending, ties by index),
+ *     x multiplied once by rw and y by rh, ratios [N][2] f32 (rh, rw) on the device; NULL: no rescale;
+ *   out_scores [N][D], out_labels [N][D] int64; counts [N] int32 = cnt.
+ * Every element of every output is written; slots past cnt are 0. num_keep < 0 (an NMS segment over
+ * max_seg) sets every count to -1, so a failed NMS never passes for an empty result. n == 0 is
+ * allowed (keep and the candidate arrays may then be NULL). */
+int mx_det_select(const int64_t* keep, const int64_t* num_keep, const float* boxes, const float* scores,
+                  const int64_t* labels, const int32_t* grp, int64_t n, int64_t N, int64_t D, const float* ratios,
+                  float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* counts, mx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Corruption augmentation (scripts/augmentations.py:14-56, RandomCorruption :60-74), uint8 HWC.
  *   op: 0 identity, 1 noise (sigma, Philox seed; or `noise` field f32 if non-NULL), 2 motion blur
  *   (k=9, angle 0), 3 low-res (INTER_AREA x factor, INTER_LINEAR back). Batched form takes one op

@@ -1,6 +1,7 @@
 // mx_elementwise.hip — anchors, box decode, corruption augmentation, normalize+pad (gfx950).
 // Built -ffp-contract=off: every f32 op rounds once, as the restated torch / OpenCV code does.
 #include "mx_common.h"
+#include "mx_boxcoder.h"
 
 namespace mx {
 
@@ -23,18 +24,7 @@ __global__ void decode_kernel(const float4* __restrict__ rel, const float4* __re
                               float4 w, float clip, float4* __restrict__ out) {
   int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n * ncls) return;
-  int64_t i = t / ncls;
-  float4 b = boxes[i];
-  float widths = b.z - b.x, heights = b.w - b.y;
-  float cx = b.x + 0.5f * widths, cy = b.y + 0.5f * heights;
-  float4 r = rel[t];
-  float dx = r.x / w.x, dy = r.y / w.y, dw = r.z / w.z, dh = r.w / w.w;
-  dw = dw > clip ? clip : dw;
-  dh = dh > clip ? clip : dh;
-  float pcx = dx * widths + cx, pcy = dy * heights + cy;
-  float pw = expf(dw) * widths, ph = expf(dh) * heights;
-  float hw = 0.5f * pw, hh = 0.5f * ph;
-  out[t] = make_float4(pcx - hw, pcy - hh, pcx + hw, pcy + hh);
+  out[t] = decode_box(boxes[t / ncls], rel[t], w, clip);
 }
 
 // ---- corruption (scripts/augmentations.py:30-45) --------------------------------------------

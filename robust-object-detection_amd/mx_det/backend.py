@@ -185,6 +185,13 @@ class HipBackend:
     def proposal_clip_filter(self, proposals, top, prob, hw, min_size, score_thresh):
         return ops.proposal_clip_filter(proposals, top, prob, hw, min_size, score_thresh)
 
+    def detections_postprocess(self, logits, reg, rois, img, hw, N, score_thresh, nms_thresh, detections_per_img,
+                               ratios=None, weights=ops.ROI_WEIGHTS, max_seg=None):
+        """RoIHeads.postprocess_detections + the transform's box rescale for every image on the device:
+        padded (boxes [N, D, 4], scores [N, D], labels [N, D], counts [N]); no host synchronisation."""
+        return ops.detections_postprocess(logits, reg, rois, img, hw, N, score_thresh, nms_thresh, detections_per_img,
+                                          ratios, weights, max_seg)
+
     def anchors_level(self, size, ratios, gh, gw, sh, sw, device):
         return ops.anchors_level(size, ratios, gh, gw, sh, sw, device)
 

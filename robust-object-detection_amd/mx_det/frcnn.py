@@ -582,11 +582,13 @@ class RegionProposalNetwork(nn.Module):
         counts = valid.sum(1).tolist()
         return [pb[i, :c] for i, c in enumerate(counts)], [ps[i, :c] for i, c in enumerate(counts)]
 
-    def forward(self, images, features, targets=None, be=None, head=None, defer_losses=False):
+    def forward(self, images, features, targets=None, be=None, head=None, defer_losses=False, padded=False):
         """torchvision RegionProposalNetwork.forward -> (proposals, losses). defer_losses=True returns a
         callable in place of the losses dict: the caller issues the shape-independent target / sampler
         / loss launches later (FasterRCNN.forward: right after the RoI sampler's host sync, so the GPU
-        works on them while the host issues the RoI head instead of idling)."""
+        works on them while the host issues the RoI head instead of idling). padded=True returns the
+        padded (boxes, scores, valid) of filter_proposals_padded in eval mode too (the fused detection
+        tail: no host sync for the per-image counts)."""
         feats = list(features.values())
         # objectness [N, A], pred_deltas [N, A, 4], anchors per level
         objectness, pred_deltas, num_per_level = head if head is not None else self.head(feats, be)
@@ -661,7 +663,7 @@ class RegionProposalNetwork(nn.Module):
             losses = compute_losses if defer_losses else compute_losses()
         proposals = be.box_decode(pred_deltas.detach().reshape(-1, 4), anchors.repeat(N, 1), RPN_WEIGHTS)
         proposals = proposals.view(N, A, 4)
-        if self.training:  # padded (boxes, scores, valid): the RoI sampler works on the device
+        if self.training or padded:  # padded (boxes, scores, valid): the RoI sampler / fused tail work on the device
             boxes = self.filter_proposals_padded(proposals, objectness, images.image_sizes, num_per_level, be)
         else:
             boxes, _ = self.filter_proposals(proposals, objectness, images.image_sizes, num_per_level, be)
@@ -788,6 +790,55 @@ class RoIHeads(nn.Module):
         self.fg_bg_sampler = BalancedPositiveNegativeSampler(batch_size_per_image, positive_fraction)
         self.score_thresh, self.nms_thresh, self.detections_per_img = score_thresh, nms_thresh, detections_per_img
         self.featmap_names = ["0", "1", "2", "3"]
+        self.fused_detections = False  # or MX_FUSED_DETECTIONS=1: the eval tail on the device (_detect_fused)
+
+    def fused_active(self, be):
+        """Eval mode with the fused detection tail switched on (fused_detections / MX_FUSED_DETECTIONS=1)
+        on a backend that has it."""
+        return (not self.training and hasattr(be, "detections_postprocess")
+                and (self.fused_detections or os.environ.get("MX_FUSED_DETECTIONS", "0") == "1"))
+
+    def _det_consts(self, N, post, image_sizes, original_sizes, dev):
+        """Per (shape, size set) device constants of the fused tail, built once (a host->device copy
+        waits for the GPU): the image index of each padded row (f32 column for RoIAlign, int32 for the
+        candidate kernel), (h, w) per image and the (rh, rw) ratios of transform.postprocess -- f32
+        original / resized as torch divides, 1.0 where the sizes are equal."""
+        sizes = tuple(map(tuple, image_sizes))
+        orig = tuple(map(tuple, original_sizes)) if original_sizes is not None else sizes
+        key = (N, post, sizes, orig, dev)
+        cache = self.__dict__.setdefault("_det_cache", {})
+        c = cache.get(key)
+        if c is None:
+            if len(cache) >= 256:  # a dataset of many distinct sizes: start over
+                cache.clear()
+            bi = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(post)
+            hw = torch.tensor(sizes, dtype=torch.float32)
+            ratios = torch.tensor(orig, dtype=torch.float32) / hw
+            c = cache[key] = (bi.to(torch.float32)[:, None], bi, hw.to(dev), ratios.to(dev))
+        return c
+
+    def _detect_fused(self, feats, proposals, image_sizes, original_sizes, be):
+        """The eval tail without per-image host work: the box head on the static N * post padded proposal
+        rows (a padded row keeps its image's index for RoIAlign and is dead, img = N, for the candidate
+        kernel), then softmax, decode, clip, filters, class-wise NMS, top detections_per_img and the
+        rescale to the original sizes on the device (be.detections_postprocess); one host sync per batch
+        reads the per-image counts."""
+        pb, _, pvalid = proposals
+        N, post = pvalid.shape
+        dev = pb.device
+        bcol, bi, hw, ratios = self._det_consts(N, post, image_sizes, original_sizes, dev)
+        boxes = pb.reshape(-1, 4)
+        scales, k_min = self._scales(feats, image_sizes)
+        x = be.multiscale_roi_align(feats, torch.cat([bcol, boxes], 1), scales, k_min)
+        class_logits, box_regression = self.box_predictor(self.box_head(x, be), be)
+        img = torch.where(pvalid.reshape(-1), bi, N)
+        ob, osc, ol, counts = be.detections_postprocess(class_logits, box_regression, boxes, img, hw, N,
+                                                        self.score_thresh, self.nms_thresh, self.detections_per_img,
+                                                        ratios=ratios, weights=ROI_WEIGHTS, max_seg=max(post, 1000))
+        counts = counts.tolist()  # the tail's one host sync
+        if any(c < 0 for c in counts):
+            raise RuntimeError("detection NMS: a class segment exceeded max_seg (num_keep < 0)")
+        return [{"boxes": ob[i, :c], "labels": ol[i, :c], "scores": osc[i, :c]} for i, c in enumerate(counts)]
 
     def _head_graph(self, x, be):
         """Box head + predictor forward/backward as two HIP graphs per RoI count (training, HIP
@@ -839,11 +890,14 @@ class RoIHeads(nn.Module):
         sm = (pos_m | neg_m).flatten()
         return box_p, lab_p, tg_p, sm, sm.sum()
 
-    def forward(self, features, proposals, image_sizes, targets=None, be=None, sampled=None):
+    def forward(self, features, proposals, image_sizes, targets=None, be=None, sampled=None, original_sizes=None):
         """sampled: the sample() outputs with the sampled count already on the host (FasterRCNN's
-        captured proposal stage), in place of matching and sampling here."""
+        captured proposal stage), in place of matching and sampling here. Eval with padded proposals
+        (a (boxes, scores, valid) tuple, fused_active): detections already scaled to original_sizes."""
         feats = [features[k] for k in self.featmap_names]
         dev = feats[0].device
+        if not self.training and isinstance(proposals, tuple):
+            return self._detect_fused(feats, proposals, image_sizes, original_sizes, be), {}
         if self.training and sampled is not None:
             box_p, lab_p, tg_p, sm, total = sampled
             cm = lab_p.shape[1]
@@ -1201,13 +1255,15 @@ class FasterRCNN(nn.Module):
         # measured 0.5 % slower than issuing them while the trunk runs (A/B on one box), so off
         defer = os.environ.get("MX_RPN_DEFER_LOSSES", "0") != "0"
         stage = self._stage(il, features, head, targets, be) if not defer else None
+        fused = self.roi_heads.fused_active(be)  # eval: the whole detection tail on the device
         try:
             if stage is not None:  # HIP-graph replay of the proposal stage (no autograd inside)
                 objectness, pred_deltas = head[0], head[1]
                 tgt, proposals, sampled = stage
                 rpn_losses = self.rpn.loss_of(objectness, pred_deltas, tgt, be)
             else:
-                proposals, rpn_losses = self.rpn(il, features, targets, be, head=head, defer_losses=defer)
+                proposals, rpn_losses = self.rpn(il, features, targets, be, head=head, defer_losses=defer,
+                                                 padded=fused)
                 sampled = None
             if degenerate is not None:
                 host, ev = degenerate
@@ -1224,7 +1280,8 @@ class FasterRCNN(nn.Module):
             gt_ready = self.rpn.__dict__.pop("_gt_ready", None)
             if gt_ready is not None:  # the RoI sampler reads the GT batch the RPN's side stream built
                 torch.cuda.current_stream().wait_event(gt_ready)
-            detections, det_losses = self.roi_heads(features, proposals, il.image_sizes, targets, be, sampled=sampled)
+            detections, det_losses = self.roi_heads(features, proposals, il.image_sizes, targets, be, sampled=sampled,
+                                                    original_sizes=original)
             self.rpn.check_nms()
         finally:  # also when the step raises: no side-stream work is left unjoined behind it
             self.rpn.join_losses()
@@ -1234,6 +1291,8 @@ class FasterRCNN(nn.Module):
             # deferred: issued after the RoI sampler's host sync, overlapping the host's RoI-head work
             losses.update(rpn_losses() if callable(rpn_losses) else rpn_losses)
             return losses
+        if fused:  # already scaled to the original sizes (mx_det_select)
+            return detections
         return self.transform.postprocess(detections, il.image_sizes, original)
 
 

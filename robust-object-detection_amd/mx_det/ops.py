@@ -563,6 +563,86 @@ def box_decode(rel_codes, boxes, weights, clip=BBOX_CLIP):
 
 
 # ---------------------------------------------------------------------------------------------
+ROI_WEIGHTS = (10.0, 10.0, 5.0, 5.0)  # torchvision RoIHeads' BoxCoder weights
+DET_MIN_SIZE = 1e-2                   # postprocess_detections' remove_small_boxes bound
+
+
+def _rows(t, width):
+    """f32 [R, >= width] with unit column stride (a column slice of a wider matrix passes as it is: the
+    kernels take the row stride)."""
+    t = t.float()
+    if t.stride(1) != 1 or t.stride(0) < width:
+        t = t.contiguous()
+    return t
+
+
+def detection_candidates(logits, reg, rois, img, hw, N, score_thresh, min_size=DET_MIN_SIZE, weights=ROI_WEIGHTS,
+                         clip=BBOX_CLIP):
+    """The front half of RoIHeads.postprocess_detections for every image in one launch
+    (mx_det_candidates): logits [R, C], reg [R, 4C], rois [R, 4], img [R] (the image of each row; outside
+    [0, N): a dead row), hw [N, 2] (h, w) f32 on the device -> dense (scores [n], boxes [n, 4] decoded and
+    clipped, labels [n] int64, grp [n] int32 = image or N when filtered out), n = R * (C - 1), entry
+    r * (C - 1) + (c - 1) for class c >= 1. No host synchronisation."""
+    _dev(logits, reg, rois, img, hw)
+    _check(logits.dim() == 2 and reg.dim() == 2, "detection_candidates: logits [R, C] and reg [R, 4C]")
+    R, C = logits.shape
+    _check(C >= 2 and reg.shape == (R, 4 * C), f"detection_candidates: C >= 2 and reg [R, 4C], got {tuple(reg.shape)}")
+    _check(rois.shape == (R, 4) and img.shape == (R,) and hw.shape == (N, 2), "detection_candidates: shapes")
+    dev = logits.device
+    n = R * (C - 1)
+    scores = torch.empty(n, dtype=torch.float32, device=dev)
+    boxes = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    labels = torch.empty(n, dtype=torch.int64, device=dev)
+    grp = torch.empty(n, dtype=torch.int32, device=dev)
+    if R:
+        lg, rg = _rows(logits, C), _rows(reg, 4 * C)
+        call("mx_det_candidates", _p(lg), lg.stride(0), _p(rg), rg.stride(0), _p(rois.float().contiguous()),
+             _p(img.to(torch.int32).contiguous()), _p(hw.float().contiguous()), R, C, int(N), (_lib.F4)(*weights),
+             float(clip), float(score_thresh), float(min_size), _p(scores), _p(boxes), _p(labels), _p(grp), _stream())
+    return scores, boxes, labels, grp
+
+
+def detection_select(keep, num_keep, boxes, scores, labels, grp, N, detections_per_img, ratios=None):
+    """The back half (mx_det_select): per image its first detections_per_img NMS survivors in keep order,
+    boxes scaled by ratios [N, 2] (rh, rw) when given -> (boxes [N, D, 4], scores [N, D], labels [N, D]
+    int64, counts [N] int32), zero past each count; every count is -1 when num_keep < 0. No host
+    synchronisation."""
+    _dev(keep, num_keep, boxes, scores, labels, grp)
+    n, D = scores.shape[0], int(detections_per_img)
+    _check(boxes.shape == (n, 4) and labels.shape == (n,) and grp.shape == (n,) and keep.shape[0] >= n,
+           "detection_select: shapes")
+    _check(D >= 1, "detection_select: detections_per_img >= 1")
+    _check(keep.dtype == torch.int64 and num_keep.dtype == torch.int64 and labels.dtype == torch.int64
+           and grp.dtype == torch.int32, "detection_select: keep / num_keep / labels int64, grp int32")
+    _check(ratios is None or (ratios.is_cuda and ratios.shape == (N, 2)),
+           "detection_select: ratios [N, 2] on the device")
+    dev = scores.device
+    ob = torch.empty((N, D, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((N, D), dtype=torch.float32, device=dev)
+    ol = torch.empty((N, D), dtype=torch.int64, device=dev)
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    rt = ratios.float().contiguous() if ratios is not None else None
+    call("mx_det_select", _p(keep.contiguous()), _p(num_keep), _p(boxes.float().contiguous()),
+         _p(scores.float().contiguous()), _p(labels.contiguous()), _p(grp.contiguous()), n, int(N), D, _p(rt),
+         _p(ob), _p(os_), _p(ol), _p(counts), _stream())
+    return ob, os_, ol, counts
+
+
+def detections_postprocess(logits, reg, rois, img, hw, N, score_thresh, nms_thresh, detections_per_img, ratios=None,
+                           weights=ROI_WEIGHTS, max_seg=None):
+    """RoIHeads.postprocess_detections + GeneralizedRCNNTransform.postprocess for all N images on the
+    device: detection_candidates -> batched_nms_grouped by label (torchvision's per-image dispatch rule)
+    -> detection_select. Returns (boxes [N, D, 4], scores [N, D], labels [N, D], counts [N] int32), padded
+    with zeros; a negative count reports an NMS segment over max_seg (default: a bound that cannot be
+    exceeded, max(R, 1000); the rows per image when the caller knows them). No host synchronisation."""
+    R, C = logits.shape
+    scores, boxes, labels, grp = detection_candidates(logits, reg, rois, img, hw, N, score_thresh, weights=weights)
+    ms = max(int(max_seg) if max_seg else R, 1000)
+    keep, nk = batched_nms_grouped(boxes, scores, labels, grp, N, C, nms_thresh, ms)
+    return detection_select(keep, nk, boxes, scores, labels, grp, N, detections_per_img, ratios)
+
+
+# ---------------------------------------------------------------------------------------------
 CORRUPT_NONE, CORRUPT_NOISE, CORRUPT_BLUR, CORRUPT_LOWRES = 0, 1, 2, 3
 
 
