@@ -711,6 +711,34 @@ int mx_jpeg_reconstruct(const int16_t* coefs, const mx_jpeg_info* info, void* ws
                         int bgr, mx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Windowed reconstruct (the U-Net patch loader: train_restoration.py:63-111 keeps one patch_size
+ * crop of each frame): the pixels of a window of the frame from the coefficients, with work and HBM
+ * traffic proportional to the window. No workspace: no full-frame component plane is written.
+ *   mx_jpeg_reconstruct_window  device: out[r][c][0..2] (uint8, rows out_row_bytes apart) for r < h,
+ *                         c < w = full[y0 + r][x0 + (hflip ? w - 1 - c : c)], where full is what
+ *                         mx_jpeg_reconstruct writes for the same coefs, info and bgr -- bit for
+ *                         bit, for 4:4:4 / 4:2:2 / 4:2:0 / grey and any window inside the frame
+ *                         (need not be MCU aligned; 1x1 is fine). out_row_bytes >= 3 * w lets a
+ *                         patch go straight into slot b of a [B][S][S][3] batch; no byte outside the
+ *                         h rows of 3 * w bytes is touched. One workgroup per 32x32 tile of the image
+ *                         grid loads (16 B per lane) only the luma blocks of its part of the window
+ *                         and the chroma blocks under it plus the one-sample halo of the fancy
+ *                         upsampling, runs the islow IDCT with 8 lanes per block into LDS planes,
+ *                         then upsamples, converts and stores. The fancy / replicate switch and the
+ *                         edge clamps are the image's, never the window's. MX_EINVAL before any HIP
+ *                         call for null pointers, an unparsed or inconsistent info, w <= 0 or
+ *                         h <= 0, a window not inside [0, width) x [0, height), out_row_bytes <
+ *                         3 * w, coefs not 16-byte aligned.
+ *   mx_jpeg_window_cover  host: cover[c] = (bx0, by0, bx1, by1), high end exclusive: the blocks of
+ *                         component c that hold a sample the window reads, halo included (all 0 for
+ *                         the absent components of a grey frame). The function the kernel calls for
+ *                         each tile's part of the window. MX_EINVAL as above.
+ * ------------------------------------------------------------------------------------------- */
+int mx_jpeg_reconstruct_window(const int16_t* coefs, const mx_jpeg_info* info, int x0, int y0, int w, int h, int hflip,
+                               int bgr, uint8_t* out, int64_t out_row_bytes, mx_stream_t stream);
+int mx_jpeg_window_cover(const mx_jpeg_info* info, int x0, int y0, int w, int h, int32_t cover[3][4]);
+
+/* ---------------------------------------------------------------------------------------------
  * Entropy decoding on the device: the scan of a file mx_jpeg_parse accepts (1 or 3 components, any
  * accepted sampling, custom Huffman tables, restart intervals) -> the coefficients
  * mx_jpeg_decode_coefs produces, bit for bit, whenever the status word is 0. A Huffman stream

@@ -11,7 +11,9 @@
 //                    h2v2_fancy_upsample: triangle filter, rows beyond the image replicated like
 //                    jdmainct.c's context rows; plain replication when downsampled_width <= 2) and
 //                    ycc_rgb_convert (jdcolor.c tables, SCALEBITS 16), grey replicated to RGB.
-// Both are integer kernels (no float anywhere), HBM-bound streaming work.
+//   window_kernel    both stages for a window of the frame in one launch, through LDS instead of the
+//                    component planes (mx_jpeg_reconstruct_window, below the full path).
+// All are integer kernels (no float anywhere); the first two are HBM-bound streaming work.
 #include "mx_common.h"
 #include "mx_jpeg_walk.h"
 
@@ -130,32 +132,49 @@ __global__ void __launch_bounds__(256) jpeg_idct_kernel(const int16_t* __restric
 }
 
 __device__ __forceinline__ int clamp255(int x) { return x < 0 ? 0 : (x > 255 ? 255 : x); }
+__device__ __forceinline__ int sel3(const int32_t* a, int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : a[2]); }
 
-// upsampled chroma sample at output (x, y) of component c (jdsample.c)
-__device__ __forceinline__ int chroma(const uint8_t* pl, int64_t stride, int hs, int vs, int dw, int dh, int x, int y) {
-  if (hs == 1 && vs == 1) return pl[(int64_t)y * stride + x];
+// upsampled chroma sample at output (x, y) of a component whose plane sample (row, col) is at(row, col)
+// (jdsample.c). The dw > 2 switch and the clamps are those of the image: dw, dh are the component's
+// downsampled size, whatever part of the plane `at` can reach.
+template <typename P>
+__device__ __forceinline__ int chroma_at(P at, int hs, int vs, int dw, int dh, int x, int y) {
+  if (hs == 1 && vs == 1) return at(y, x);
   const bool fancy = dw > 2;
-  if (!fancy) return pl[(int64_t)(y / vs) * stride + x / hs];  // h2v1_upsample / h2v2_upsample: replicate
+  if (!fancy) return at(y / vs, x / hs);  // h2v1_upsample / h2v2_upsample: replicate
   const int cx = x >> 1;
   if (vs == 1) {  // h2v1 fancy
-    const uint8_t* row = pl + (int64_t)y * stride;
-    const int v0 = row[cx];
-    if ((x & 1) == 0) return cx == 0 ? v0 : (v0 * 3 + row[cx - 1] + 1) >> 2;
-    return cx == dw - 1 ? v0 : (v0 * 3 + row[cx + 1] + 2) >> 2;
+    const int v0 = at(y, cx);
+    if ((x & 1) == 0) return cx == 0 ? v0 : (v0 * 3 + at(y, cx - 1) + 1) >> 2;
+    return cx == dw - 1 ? v0 : (v0 * 3 + at(y, cx + 1) + 2) >> 2;
   }
   // h2v2 fancy: the nearer sample row (3/4) and the other row (1/4), rows clamped to the image
   const int r0 = y >> 1;
   int r1 = (y & 1) ? r0 + 1 : r0 - 1;
   r1 = r1 < 0 ? 0 : (r1 > dh - 1 ? dh - 1 : r1);
-  const uint8_t* a = pl + (int64_t)r0 * stride;
-  const uint8_t* b = pl + (int64_t)r1 * stride;
-  const int cs = a[cx] * 3 + b[cx];
+  const int cs = at(r0, cx) * 3 + at(r1, cx);
   if ((x & 1) == 0) {
     if (cx == 0) return (cs * 4 + 8) >> 4;
-    return (cs * 3 + a[cx - 1] * 3 + b[cx - 1] + 8) >> 4;
+    return (cs * 3 + at(r0, cx - 1) * 3 + at(r1, cx - 1) + 8) >> 4;
   }
   if (cx == dw - 1) return (cs * 4 + 7) >> 4;
-  return (cs * 3 + a[cx + 1] * 3 + b[cx + 1] + 7) >> 4;
+  return (cs * 3 + at(r0, cx + 1) * 3 + at(r1, cx + 1) + 7) >> 4;
+}
+
+// the same over a whole component plane in memory
+__device__ __forceinline__ int chroma(const uint8_t* pl, int64_t stride, int hs, int vs, int dw, int dh, int x, int y) {
+  return chroma_at([=](int r, int c) -> int { return pl[(int64_t)r * stride + c]; }, hs, vs, dw, dh, x, y);
+}
+
+// jdcolor.c build_ycc_rgb_table (FIX(x) = (int)(x * 65536 + 0.5), ONE_HALF = 1 << 15)
+__device__ __forceinline__ void ycc_rgb(int Y, int cb, int cr, int& R, int& G, int& B) {
+  const int xcr = cr - 128, xcb = cb - 128;
+  const int crr = (91881 * xcr + 32768) >> 16;
+  const int cbb = (116130 * xcb + 32768) >> 16;
+  const int g = (-46802 * xcr + (-22554 * xcb + 32768)) >> 16;
+  R = clamp255(Y + crr);
+  G = clamp255(Y + g);
+  B = clamp255(Y + cbb);
 }
 
 __global__ void __launch_bounds__(256) jpeg_colour_kernel(const uint8_t* __restrict__ planes, JpegDev j, int bgr,
@@ -171,14 +190,7 @@ __global__ void __launch_bounds__(256) jpeg_colour_kernel(const uint8_t* __restr
     const int hs = j.hmax / j.h[1], vs = j.vmax / j.v[1];  // chroma components share one sampling
     const int cb = chroma(planes + j.plane_off[1], (int64_t)j.bw[1] * 8, hs, vs, j.dw[1], j.dh[1], x, y);
     const int cr = chroma(planes + j.plane_off[2], (int64_t)j.bw[2] * 8, hs, vs, j.dw[2], j.dh[2], x, y);
-    // jdcolor.c build_ycc_rgb_table (FIX(x) = (int)(x * 65536 + 0.5), ONE_HALF = 1 << 15)
-    const int xcr = cr - 128, xcb = cb - 128;
-    const int crr = (91881 * xcr + 32768) >> 16;
-    const int cbb = (116130 * xcb + 32768) >> 16;
-    const int g = (-46802 * xcr + (-22554 * xcb + 32768)) >> 16;
-    R = clamp255(Y + crr);
-    G = clamp255(Y + g);
-    B = clamp255(Y + cbb);
+    ycc_rgb(Y, cb, cr, R, G, B);
   }
   uint8_t* o = out + i * 3;
   o[0] = (uint8_t)(bgr ? B : R);
@@ -239,6 +251,239 @@ extern "C" int mx_jpeg_reconstruct(const int16_t* coefs, const mx_jpeg_info* inf
   MX_LAUNCH_CHECK();
   const int64_t np = (int64_t)j.width * j.height;
   jpeg_colour_kernel<<<(unsigned)cdiv(np, 256), 256, 0, st>>>((const uint8_t*)ws, j, bgr, out);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+// ================================================================================================
+// Windowed reconstruct: the pixels of a window of the frame straight from the coefficients, without
+// the full-frame component planes (mx_jpeg_reconstruct_window; the U-Net patch loader keeps a 256x256
+// crop of a 1920x1080 frame). One workgroup per 32x32-pixel tile of the IMAGE grid (a multiple of
+// every accepted MCU, so a tile's luma blocks are whole blocks); the part of the tile inside the
+// window is its rectangle. jpeg_window_cover() names the blocks of each component that rectangle
+// reads: its luma blocks, and the chroma blocks under it plus the one-sample halo of the fancy
+// upsampling (at most 4 x 4 blocks per component). The workgroup loads those blocks (16 B per lane),
+// runs the islow IDCT with 8 lanes per block (column pass, then row pass, through LDS) into LDS
+// planes, and after a barrier every lane upsamples, converts and stores its pixels with the
+// arithmetic of the full path (idct8, descale, idct_limit, chroma_at, ycc_rgb). The fancy / replicate
+// switch and the edge clamps are the image's (dw, dh), never the tile's: at a tile or window edge
+// inside the image the neighbour sample is real data from the halo block.
+// ================================================================================================
+namespace mx {
+
+constexpr int kWinTile = 32;    // pixels a side
+constexpr int kWinPitch = 40;   // bytes per row of an LDS plane: 4 blocks across + 8 (8-B aligned rows)
+constexpr int kWinSlots = 32;   // blocks per IDCT round: 256 lanes / 8
+constexpr int kWinWsPitch = 65; // words per block of the IDCT workspace: the 8 blocks of a wave on 8 banks
+
+struct JpegWinGeom {
+  int32_t ncomp, hs, vs, dw, dh;  // chroma upsampling factors and downsampled size (both chroma components)
+};
+
+// Blocks (bx0, by0, bx1, by1; high end exclusive) of every component that hold a sample the pixels
+// [x0, x1] x [y0, y1] (inclusive, inside the image) read: chroma_at()'s taps restated as ranges.
+__host__ __device__ inline void jpeg_window_cover(const JpegWinGeom& g, int x0, int y0, int x1, int y1,
+                                                  int32_t cover[3][4]) {
+  cover[0][0] = x0 >> 3;
+  cover[0][1] = y0 >> 3;
+  cover[0][2] = (x1 >> 3) + 1;
+  cover[0][3] = (y1 >> 3) + 1;
+  int cl = x0, cr = x1, rt = y0, rb = y1;  // chroma sample columns / rows, inclusive
+  if (g.hs == 1 && g.vs == 1) {
+  } else if (g.dw <= 2) {  // replicate
+    cl = x0 / g.hs;
+    cr = x1 / g.hs;
+    rt = y0 / g.vs;
+    rb = y1 / g.vs;
+  } else {
+    cl = x0 >> 1;
+    if ((x0 & 1) == 0 && cl > 0) --cl;  // an even column reads its left neighbour
+    cr = x1 >> 1;
+    if ((x1 & 1) == 1 && cr < g.dw - 1) ++cr;  // an odd column its right one
+    if (g.vs == 2) {
+      rt = y0 >> 1;
+      if ((y0 & 1) == 0 && rt > 0) --rt;
+      rb = y1 >> 1;
+      if ((y1 & 1) == 1 && rb < g.dh - 1) ++rb;
+    }
+  }
+  for (int c = 1; c < 3; ++c) {
+    const bool on = g.ncomp == 3;
+    cover[c][0] = on ? cl >> 3 : 0;
+    cover[c][1] = on ? rt >> 3 : 0;
+    cover[c][2] = on ? (cr >> 3) + 1 : 0;
+    cover[c][3] = on ? (rb >> 3) + 1 : 0;
+  }
+}
+
+__global__ void __launch_bounds__(256) jpeg_window_kernel(const int16_t* __restrict__ coefs, JpegDev j, int x0, int y0,
+                                                          int w, int h, int hflip, int bgr, uint8_t* __restrict__ out,
+                                                          int64_t out_row_bytes) {
+  __shared__ __attribute__((aligned(16))) uint8_t pl[3][kWinTile * kWinPitch];
+  __shared__ int ws[kWinSlots * kWinWsPitch];
+  __shared__ uint16_t qd[3][64];
+  const int t = threadIdx.x;
+  const int X = ((x0 >> 5) + (int)blockIdx.x) * kWinTile, Y = ((y0 >> 5) + (int)blockIdx.y) * kWinTile;
+  // the tile's rectangle: its pixels inside the window
+  const int rx0 = max(X, x0), ry0 = max(Y, y0);
+  const int rx1 = min(X + kWinTile - 1, x0 + w - 1), ry1 = min(Y + kWinTile - 1, y0 + h - 1);
+  JpegWinGeom g;
+  g.ncomp = j.ncomp;
+  g.hs = j.hmax / j.h[1];  // chroma components share one sampling
+  g.vs = j.vmax / j.v[1];
+  g.dw = j.dw[1];
+  g.dh = j.dh[1];
+  int32_t cov[3][4];
+  jpeg_window_cover(g, rx0, ry0, rx1, ry1, cov);
+  const int lbx0 = cov[0][0], lby0 = cov[0][1], lnx = cov[0][2] - cov[0][0];
+  const int cbx0 = cov[1][0], cby0 = cov[1][1], cnx = cov[1][2] - cov[1][0];
+  const int nb0 = lnx * (cov[0][3] - cov[0][1]);
+  const int nb1 = cnx * (cov[1][3] - cov[1][1]);  // 0 for a grey frame; the two chroma covers are equal
+  const int nblk = nb0 + 2 * nb1;
+  if (t < 192) qd[t >> 6][t & 63] = j.qt[sel3(j.tq, t >> 6)][t & 63];
+  __syncthreads();
+  // ---- dequantisation + jpeg_idct_islow, 8 lanes per block, 32 blocks per round
+  const int l = t & 7, slot = t >> 3;
+  int* wsb = &ws[slot * kWinWsPitch];
+  for (int base = 0; base < nblk; base += kWinSlots) {
+    int k = base + slot;
+    const bool on = k < nblk;
+    int c = 0;
+    if (k >= nb0) {
+      k -= nb0;
+      c = 1;
+      if (k >= nb1) {
+        k -= nb1;
+        c = 2;
+      }
+    }
+    const int nx = c == 0 ? lnx : cnx;
+    const int by = on ? k / nx : 0, bx = on ? k - by * nx : 0;  // inside the component's cover
+    if (on) {
+      const int64_t gb = (int64_t)((c == 0 ? lby0 : cby0) + by) * sel3(j.bw, c) + (c == 0 ? lbx0 : cbx0) + bx;
+      const int64_t off = c == 0 ? j.coef_off[0] : (c == 1 ? j.coef_off[1] : j.coef_off[2]);
+      const uint4 u = *(const uint4*)(coefs + off + gb * 64 + l * 8);  // row l of the block
+      const uint32_t uw[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) wsb[l * 8 + e] = (int)(int16_t)((uw[e >> 1] >> ((e & 1) * 16)) & 0xffff);
+    }
+    __syncthreads();
+    if (on) {  // pass 1: column l (DEQUANTIZE = coef * q), outputs descaled by CONST_BITS - PASS1_BITS
+      int64_t in[8], o[8];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) in[r] = (int64_t)wsb[r * 8 + l] * qd[c][r * 8 + l];
+      idct8(in, o);
+#pragma unroll
+      for (int r = 0; r < 8; ++r) wsb[r * 8 + l] = (int32_t)descale(o[r], 11);
+    }
+    __syncthreads();
+    if (on) {  // pass 2: row l, descaled by CONST_BITS + PASS1_BITS + 3, range-limited
+      int64_t in[8], o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) in[e] = (int64_t)wsb[l * 8 + e];
+      idct8(in, o);
+      uint32_t lo = 0, hi = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        lo |= (uint32_t)idct_limit(descale(o[e], 18)) << (8 * e);
+        hi |= (uint32_t)idct_limit(descale(o[e + 4], 18)) << (8 * e);
+      }
+      *(uint2*)&pl[c][(by * 8 + l) * kWinPitch + bx * 8] = make_uint2(lo, hi);
+    }
+    __syncthreads();
+  }
+  // ---- upsampling + colour conversion from the LDS planes; lanes outside the rectangle store nothing
+  const int hs = g.hs, vs = g.vs, dw = g.dw, dh = g.dh;
+  const int x = X + (t & 31);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int y = Y + (t >> 5) + 8 * q;
+    if (x < rx0 || x > rx1 || y < ry0 || y > ry1) continue;
+    const int Yv = pl[0][(y - lby0 * 8) * kWinPitch + (x - lbx0 * 8)];
+    int R, G, B;
+    if (j.ncomp == 1) {
+      R = G = B = Yv;
+    } else {
+      const uint8_t* p1 = pl[1];
+      const uint8_t* p2 = pl[2];
+      const int cb = chroma_at([=](int r, int cc) -> int { return p1[(r - cby0 * 8) * kWinPitch + (cc - cbx0 * 8)]; },
+                               hs, vs, dw, dh, x, y);
+      const int cr = chroma_at([=](int r, int cc) -> int { return p2[(r - cby0 * 8) * kWinPitch + (cc - cbx0 * 8)]; },
+                               hs, vs, dw, dh, x, y);
+      ycc_rgb(Yv, cb, cr, R, G, B);
+    }
+    const int col = hflip ? w - 1 - (x - x0) : x - x0;
+    uint8_t* o = out + (int64_t)(y - y0) * out_row_bytes + (int64_t)col * 3;
+    o[0] = (uint8_t)(bgr ? B : R);
+    o[1] = (uint8_t)G;
+    o[2] = (uint8_t)(bgr ? R : B);
+  }
+}
+
+// what both window entry points require of (info, window); nullptr when fine
+static const char* win_check(const mx_jpeg_info* info, int x0, int y0, int w, int h, JpegWinGeom* g) {
+  if (!info) return "null argument";
+  if (info->ncomp != 1 && info->ncomp != 3) return "1 or 3 components";
+  if (info->width <= 0 || info->height <= 0 || info->coef_total <= 0) return "parse the image first";
+  if (w <= 0 || h <= 0) return "empty window";
+  if (x0 < 0 || y0 < 0 || (int64_t)x0 + w > info->width || (int64_t)y0 + h > info->height)
+    return "window outside the image";
+  g->ncomp = info->ncomp;
+  g->hs = g->vs = 1;
+  g->dw = g->dh = 0;
+  if (info->ncomp == 3) {
+    const int h0 = info->h[0], v0 = info->v[0];
+    const bool ok = info->h[1] == 1 && info->v[1] == 1 && info->h[2] == 1 && info->v[2] == 1 && info->hmax == h0 &&
+                    info->vmax == v0 && ((h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2));
+    if (!ok) return "chroma subsampling 4:4:4, 4:2:2 or 4:2:0 only";
+    g->hs = h0;
+    g->vs = v0;
+    g->dw = info->dw[1];
+    g->dh = info->dh[1];
+    if (info->dw[2] != g->dw || info->dh[2] != g->dh || g->dw != (info->width + h0 - 1) / h0 ||
+        g->dh != (info->height + v0 - 1) / v0)
+      return "inconsistent downsampled size";
+  }
+  // every block the window can name lies inside the coefficient layout
+  int32_t cov[3][4];
+  jpeg_window_cover(*g, 0, 0, info->width - 1, info->height - 1, cov);
+  int64_t off = 0;
+  for (int c = 0; c < info->ncomp; ++c) {
+    if (cov[c][2] > info->bw[c] || cov[c][3] > info->bh[c] || info->coef_off[c] != off || info->tq[c] < 0 ||
+        info->tq[c] > 3)
+      return "inconsistent block layout";
+    off += (int64_t)info->bw[c] * info->bh[c] * 64;
+  }
+  if (off != info->coef_total) return "inconsistent coefficient total";
+  return nullptr;
+}
+
+}  // namespace mx
+
+extern "C" int mx_jpeg_window_cover(const mx_jpeg_info* info, int x0, int y0, int w, int h, int32_t cover[3][4]) {
+  MX_CHECK_ARG(cover, "jpeg_window_cover: null argument");
+  JpegWinGeom g;
+  const char* bad = win_check(info, x0, y0, w, h, &g);
+  MX_CHECK_ARG(!bad, "jpeg_window_cover: %s", bad);
+  jpeg_window_cover(g, x0, y0, x0 + w - 1, y0 + h - 1, cover);
+  return MX_OK;
+}
+
+extern "C" int mx_jpeg_reconstruct_window(const int16_t* coefs, const mx_jpeg_info* info, int x0, int y0, int w, int h,
+                                          int hflip, int bgr, uint8_t* out, int64_t out_row_bytes, mx_stream_t stream) {
+  MX_CHECK_ARG(coefs && info && out, "jpeg_reconstruct_window: null argument");
+  JpegWinGeom g;
+  const char* bad = win_check(info, x0, y0, w, h, &g);
+  MX_CHECK_ARG(!bad, "jpeg_reconstruct_window: %s", bad);
+  MX_CHECK_ARG(out_row_bytes >= (int64_t)3 * w, "jpeg_reconstruct_window: out_row_bytes below 3 * w = %lld",
+               (long long)3 * w);
+  MX_CHECK_ARG(((uintptr_t)coefs & 15) == 0, "jpeg_reconstruct_window: coefficients must be 16-byte aligned");
+  JpegDev j;
+  int64_t unused = 0;
+  to_dev(info, &j, &unused);
+  const dim3 grid((unsigned)(((x0 + w - 1) >> 5) - (x0 >> 5) + 1), (unsigned)(((y0 + h - 1) >> 5) - (y0 >> 5) + 1));
+  jpeg_window_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(coefs, j, x0, y0, w, h, hflip ? 1 : 0, bgr ? 1 : 0, out,
+                                                          out_row_bytes);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }
@@ -491,8 +736,6 @@ __device__ constexpr int kZig[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32,
                                      12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
                                      35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
                                      58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-__device__ __forceinline__ int sel3(const int32_t* a, int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : a[2]); }
 
 // scan-order block s -> component, coefficient offset of the block and of the block whose DC is its
 // predictor (-1: none, the first block of the component)

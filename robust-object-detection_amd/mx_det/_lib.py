@@ -120,6 +120,8 @@ _SIGS = {
     "mx_jpeg_decode_coefs": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "mx_jpeg_workspace": (c_sz, [c_vp]),
     "mx_jpeg_reconstruct": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_int, c_vp]),
+    "mx_jpeg_reconstruct_window": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
+    "mx_jpeg_window_cover": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp]),
     "mx_jpeg_entropy_decode_workspace": (c_sz, [c_vp, c_i64]),
     "mx_jpeg_entropy_decode": (c_int, [c_vp, c_i64, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "mx_jpeg_entropy_decode_set_subseq": (c_int, [c_int]),

@@ -17,6 +17,10 @@ libjpeg-turbo's default decode -- PIL Image.open(p).convert("RGB") (coco_detecti
 with bgr=True cv2.imread (restore_testsets.py:99). Progressive / arithmetic / CMYK / 4:4:0 files raise
 NotImplementedError (MX_EUNSUPPORTED); callers that must accept them decode those on the host.
 
+A window of the frame (reconstruct_window / decode_window, mx_jpeg_reconstruct_window) is reconstructed
+from the same coefficients without the rest: the U-Net patch loader (mx_det.restoration) keeps one crop
+per frame.
+
 Encode (encode / write_file / encode_coefs, below) runs wholly on the device -- pixel stage and
 entropy coder -- and is byte-identical to PIL's Image.save(format="JPEG", quality, subsampling).
 """
@@ -198,6 +202,60 @@ def decode(data, device, bgr=False, pin=True, entropy="host"):
         return device_stage(*host_stage(data), device, bgr)
     info, coefs = decode_coefs(data)
     return _reconstruct(info, torch.from_numpy(coefs).to(device), device, bgr)
+
+
+# ------------------------------------------------------------------------------------------ window
+def window_cover(info, box):
+    """Blocks each component of `info` needs for the window box = (x0, y0, w, h), the fancy
+    upsampling's one-sample halo included: an int32 [3, 4] array of (bx0, by0, bx1, by1), high end
+    exclusive (zeros for the absent components of a grey frame). Host only (mx_jpeg_window_cover: the
+    function the kernel calls per tile)."""
+    x0, y0, w, h = (int(v) for v in box)
+    cover = np.zeros((3, 4), dtype=np.int32)
+    rc = _lib.load().mx_jpeg_window_cover(ctypes.byref(info), x0, y0, w, h, cover.ctypes.data)
+    if rc != 0:
+        raise ValueError(_lib.load().mx_last_error().decode())
+    return cover
+
+
+def reconstruct_window(info, coefs_dev, box, hflip=False, bgr=False, out=None):
+    """The window box = (x0, y0, w, h) of the frame from its device coefficients (decode_coefs' layout)
+    -> uint8 [h, w, 3] on the device: decode(...)[y0:y0 + h, x0:x0 + w], flipped left-right with
+    hflip, bit for bit, with work proportional to the window (mx_jpeg_reconstruct_window, on the
+    current stream). out: a uint8 [h, w, 3] device tensor to fill instead, dense inside a row but with
+    any row stride (batch[b], or a column range of it)."""
+    x0, y0, w, h = (int(v) for v in box)
+    if out is None:
+        out = torch.empty((max(h, 0), max(w, 0), 3), dtype=torch.uint8, device=coefs_dev.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == coefs_dev.device
+              and tuple(out.shape) == (h, w, 3) and out.stride(2) == 1 and out.stride(1) == 3
+              and (h <= 1 or out.stride(0) >= 3 * w)):
+        raise ValueError("reconstruct_window: out must be a uint8 [h, w, 3] tensor on the coefficients' device with "
+                         "dense rows")
+    if coefs_dev.dtype != torch.int16 or coefs_dev.numel() < info.coef_total or not coefs_dev.is_contiguous():
+        raise ValueError("reconstruct_window: coefs_dev must be a contiguous int16 tensor of coef_total elements")
+    row_bytes = out.stride(0) if h > 1 else max(out.stride(0), 3 * w)
+    _lib.call("mx_jpeg_reconstruct_window", coefs_dev.data_ptr(), ctypes.byref(info), x0, y0, w, h, int(bool(hflip)),
+              int(bool(bgr)), out.data_ptr(), row_bytes, _lib.stream())
+    return out
+
+
+def decode_window(data, device, box, hflip=False, bgr=False, entropy="host"):
+    """JPEG bytes -> the window box = (x0, y0, w, h) of the decoded frame, uint8 [h, w, 3] on `device`:
+    decode(data, device, bgr)[y0:y0 + h, x0:x0 + w] (flipped left-right with hflip) without
+    reconstructing the rest of the frame. The entropy decode covers the whole scan, on the host or the
+    device as in decode(); a file the device decoder flags goes through the host entropy path."""
+    if entropy not in ("host", "device"):
+        raise ValueError("decode_window: entropy is 'host' or 'device'")
+    if entropy == "device":
+        info, host = host_stage_bytes(data)
+        r = entropy_stage(info, host, device)
+        if r is not None:
+            out = reconstruct_window(info, r[0], box, hflip, bgr)
+            if int(r[1].item()) == 0:
+                return out
+    info, host = host_stage(data)
+    return reconstruct_window(info, host.to(device, non_blocking=True), box, hflip, bgr)
 
 
 def read_file(path, device, bgr=False):

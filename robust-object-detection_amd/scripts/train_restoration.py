@@ -8,6 +8,10 @@ restore_testsets load them unchanged. The U-Net forward/backward runs on the HIP
 bf16x3 conv products by default, MX_PRECISION=bf16 for bf16); the corruption of each batch runs on
 the device (mx_det.restoration.RestorationBatcher); the optimizer is mx_det.optim.AdamW (one launch
 that also writes the next forward's conv operands; MX_ADAMW=0 for torch.optim.AdamW).
+MX_PATCH_LOADER=host (the default) reads the patches as the reference does: PIL decodes every whole
+frame in the training thread. MX_PATCH_LOADER=device decodes them on the device ahead of the step
+(mx_det.restoration.DevicePatchLoader: only the crop is reconstructed; MX_JPEG_DECODE picks where the
+entropy decode runs); for a given seed its patch sequence differs from the host loader's.
 """
 import json
 import os
@@ -18,8 +22,8 @@ import torch
 
 from mx_det import optim as mx_optim
 from mx_det.engine import init_device, set_seed
-from mx_det.restoration import (CombinedLoss, RestorationBatcher, RestorationDataset, collate_u8, train_epoch,
-                                validate)
+from mx_det.restoration import (CombinedLoss, DevicePatchLoader, RestorationBatcher, RestorationDataset, collate_u8,
+                                train_epoch, validate)
 from mx_det.unet import RestorationUNet
 
 SEED = 42
@@ -40,17 +44,26 @@ def save_jsonl(path, record):
 
 
 def main(train_dir=TRAIN_IMG_DIR, val_dir=VAL_IMG_DIR, out_dir=OUT_DIR, epochs=EPOCHS):
+    patch_loader = os.environ.get("MX_PATCH_LOADER", "host")
+    if patch_loader not in ("host", "device"):
+        raise ValueError("MX_PATCH_LOADER is 'host' or 'device'")
     set_seed(SEED)
     dev, _, _ = init_device()
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     print(f"Device: {dev}\nTraining image restoration model (U-Net)", flush=True)
-    train_ds = RestorationDataset(train_dir, PATCH_SIZE, is_train=True)
-    val_ds = RestorationDataset(val_dir, PATCH_SIZE, is_train=False)
-    train_loader = torch.utils.data.DataLoader(train_ds, batch_size=BATCH_SIZE, shuffle=True, num_workers=NUM_WORKERS,
-                                               pin_memory=True, drop_last=True, collate_fn=collate_u8)
-    val_loader = torch.utils.data.DataLoader(val_ds, batch_size=BATCH_SIZE, shuffle=False, num_workers=NUM_WORKERS,
-                                             pin_memory=True, collate_fn=collate_u8)
+    if patch_loader == "device":
+        train_loader = DevicePatchLoader(train_dir, PATCH_SIZE, BATCH_SIZE, True, dev, shuffle=True, drop_last=True)
+        val_loader = DevicePatchLoader(val_dir, PATCH_SIZE, BATCH_SIZE, False, dev, shuffle=False, drop_last=False)
+        train_ds, val_ds = train_loader.dataset, val_loader.dataset
+    else:
+        train_ds = RestorationDataset(train_dir, PATCH_SIZE, is_train=True)
+        val_ds = RestorationDataset(val_dir, PATCH_SIZE, is_train=False)
+        train_loader = torch.utils.data.DataLoader(train_ds, batch_size=BATCH_SIZE, shuffle=True,
+                                                   num_workers=NUM_WORKERS, pin_memory=True, drop_last=True,
+                                                   collate_fn=collate_u8)
+        val_loader = torch.utils.data.DataLoader(val_ds, batch_size=BATCH_SIZE, shuffle=False, num_workers=NUM_WORKERS,
+                                                 pin_memory=True, collate_fn=collate_u8)
     print(f"Train: {len(train_ds)} images, Val: {len(val_ds)} images", flush=True)
     model = RestorationUNet(channels=(32, 64, 128, 256)).to(dev)
     print(f"Model parameters: {sum(p.numel() for p in model.parameters()) / 1e6:.2f}M\n", flush=True)
