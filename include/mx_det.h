@@ -827,6 +827,25 @@ int mx_jpeg_entropy(const int16_t* coefs_dev, const mx_jpeg_info* info, void* ws
                     int64_t out_cap, int64_t* nbytes_dev, mx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * JPEG compression as a corruption: out[b] = the pixels libjpeg-turbo decodes from the file it writes
+ * for img[b] at quality_host[b] -- PIL's Image.open(BytesIO(save(img[b], "JPEG", quality, subsampling)))
+ * .convert("RGB"), bit for bit; with bgr = 1 both img and out are BGR. img, out: uint8 [B][H][W][3],
+ * contiguous, out not overlapping img. quality_host[b] in 1..100, or 0: out[b] is left untouched (a
+ * batch in which only some images get this corruption). subsampling 0 (4:4:4) or 2 (4:2:0), PIL's
+ * numbering as in mx_jpeg_encode_info, whose quantisation tables the kernel derives from the quality.
+ * Two launches per 64 compressed images: the pixel stage of mx_jpeg_forward continued through
+ * dequantisation and jpeg_idct_islow inside the workgroup (no coefficient reaches memory) into the
+ * component planes of ws, then chroma upsampling + YCbCr -> RGB as in mx_jpeg_reconstruct. ws:
+ * mx_corrupt_jpeg_workspace() bytes (B x the planes of one image; 0 for a bad shape), 8-byte aligned.
+ * Stream-ordered, no host synchronisation, no allocation. Every argument check precedes the first
+ * launch: MX_EINVAL for a null pointer, a quality outside 0..100, another subsampling, out == img or
+ * overlapping it, a short workspace, a side over 65535 or more than 2^28 pixels.
+ * ------------------------------------------------------------------------------------------- */
+size_t mx_corrupt_jpeg_workspace(int64_t B, int64_t H, int64_t W, int subsampling);
+int mx_corrupt_jpeg_u8(const uint8_t* img, int64_t B, int64_t H, int64_t W, const int32_t* quality_host,
+                       int subsampling, int bgr, void* ws, size_t ws_bytes, uint8_t* out, mx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * COCOeval (bbox) on the device: pycocotools' COCOeval.evaluate (computeIoU + evaluateImg) and
  * accumulate, as train_frcnn_baseline.py:92-96 and eval_all.py:131-156 call them. f64 throughout, every
  * operation rounded once and in the host code's order (maskApi bbIou; mx_det/coco.py is the restated

@@ -694,6 +694,10 @@ inline int nbits_of(int a) { return a ? 32 - __builtin_clz((unsigned)a) : 0; }
 namespace mx {
 const char* jpeg_enc_check(const mx_jpeg_info* info) { return enc_check(info); }
 
+// the Annex K base table t (0 luma, 1 chroma) mx_jpeg_encode_info scales: the round-trip kernel
+// (mx_jpeg.hip) scales the same 64 bytes on the device
+const uint8_t* jpeg_base_quant(int t) { return kBaseQ[t]; }
+
 // Encoding table of one DHT table (T.81 C.2, jchuff.c jpeg_make_c_derived_tbl): tab[symbol] =
 // code << 8 | length, 0 for a symbol without a code. Shared with the device coder (mx_jpeg.hip).
 bool jpeg_enc_table(const uint8_t* bits, const uint8_t* vals, uint32_t* tab) {

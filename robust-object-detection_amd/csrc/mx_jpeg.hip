@@ -576,28 +576,25 @@ __device__ __forceinline__ void fwd_block(int b, int& c, int& row0, int& col0) {
   }
 }
 
+// The front of the pixel stage, shared by jpeg_forward_kernel and jpeg_roundtrip_kernel: the tile at
+// (x0, y0) of the [height][width][3] image `img` -> raw (16-B chunks) -> component planes pl (colour
+// conversion, edge replication, h2v2 downsampling) -> pass 1 of jpeg_fdct_islow into ws (block pitch
+// 72 words: the 8 blocks of a wave hit 8 bank groups). Lane t works on row l = t & 7 of block
+// b = t >> 3 (component c, first plane sample (row0, col0)); ws holds every block when it returns.
 // SUB 2: 4:2:0 (luma 2x2 blocks per MCU), SUB 1: 4:4:4
 template <int SUB>
-__global__ void __launch_bounds__(256) jpeg_forward_kernel(const uint8_t* __restrict__ img, JpegFwd j,
-                                                           int16_t* __restrict__ coefs) {
+__device__ __forceinline__ void fwd_tile_pass1(const uint8_t* __restrict__ img, int width, int height, int bgr, int x0,
+                                               int y0, uint8_t* raw, uint8_t (*pl)[16][64], int* ws, int& c, int& row0,
+                                               int& col0) {
   constexpr int ROWS = 8 * SUB;  // pixel rows of the tile
-  constexpr int G = SUB == 2 ? 4 : 8;  // MCUs of the tile
-  __shared__ __attribute__((aligned(16))) uint8_t raw[16 * kRawPitch];
-  __shared__ __attribute__((aligned(16))) uint8_t pl[3][16][64];
-  __shared__ int ws[kFwdBlocks * 72];  // pass-1 output, block pitch 72 words: the 8 blocks of a wave hit 8 bank groups
-  __shared__ __attribute__((aligned(16))) int16_t outc[kFwdBlocks * 64];
-  __shared__ uint16_t qd[3][64];
   const int t = threadIdx.x;
-  const int tx = blockIdx.x, my = blockIdx.y;
-  const int x0 = tx * 64, y0 = my * ROWS;
-  const int xmax = min(63, j.width - 1 - x0), rmax = min(ROWS - 1, j.height - 1 - y0);
-  if (t < 192) qd[t >> 6][t & 63] = j.qt[t >> 6][t & 63];
+  const int xmax = min(63, width - 1 - x0), rmax = min(ROWS - 1, height - 1 - y0);
   // ---- pixels -> LDS in 16-B chunks aligned in memory; chunks that straddle the tensor go by bytes
-  const uintptr_t base = (uintptr_t)img, end = base + (uintptr_t)j.width * j.height * 3;
+  const uintptr_t base = (uintptr_t)img, end = base + (uintptr_t)width * height * 3;
   {
     const int r = t / 14, ch = t % 14;
     if (r <= rmax) {
-      const uintptr_t a = base + ((uintptr_t)(y0 + r) * j.width + x0) * 3;
+      const uintptr_t a = base + ((uintptr_t)(y0 + r) * width + x0) * 3;
       const uintptr_t stop = a + (uintptr_t)(xmax + 1) * 3;
       const uintptr_t p = (a & ~(uintptr_t)15) + 16 * ch;
       if (p < stop) {
@@ -616,11 +613,11 @@ __global__ void __launch_bounds__(256) jpeg_forward_kernel(const uint8_t* __rest
   __syncthreads();
   // ---- colour conversion (+ chroma downsampling) into the component planes
   auto px = [&](int r, int x, int& R, int& Gc, int& B) {
-    const int off = (int)((base + ((uintptr_t)(y0 + r) * j.width + x0) * 3) & 15);
+    const int off = (int)((base + ((uintptr_t)(y0 + r) * width + x0) * 3) & 15);
     const uint8_t* p = &raw[r * kRawPitch + off + 3 * x];
-    R = p[j.bgr ? 2 : 0];
+    R = p[bgr ? 2 : 0];
     Gc = p[1];
-    B = p[j.bgr ? 0 : 2];
+    B = p[bgr ? 0 : 2];
   };
   if (SUB == 2) {
     const int qy = t >> 5, qx = t & 31;
@@ -635,7 +632,7 @@ __global__ void __launch_bounds__(256) jpeg_forward_kernel(const uint8_t* __rest
       }
     // chroma: the last DOWNSAMPLED row is the one replicated; inside it an odd image height repeats
     // the last pixel row
-    const int cy = min(y0 / 2 + qy, (j.height + 1) / 2 - 1);
+    const int cy = min(y0 / 2 + qy, (height + 1) / 2 - 1);
     const int ra = 2 * cy - y0;
     int cb = 0, cr = 0;
 #pragma unroll
@@ -664,7 +661,6 @@ __global__ void __launch_bounds__(256) jpeg_forward_kernel(const uint8_t* __rest
   __syncthreads();
   // ---- jpeg_fdct_islow pass 1: one block row per lane
   const int b = t >> 3, l = t & 7;
-  int c = 0, row0 = 0, col0 = 0;
   if (b < kFwdBlocks) {
     fwd_block<SUB>(b, c, row0, col0);
     const uint2 s = *(const uint2*)&pl[c][row0 + l][col0];
@@ -679,19 +675,46 @@ __global__ void __launch_bounds__(256) jpeg_forward_kernel(const uint8_t* __rest
     for (int k = 0; k < 8; ++k) ws[b * 72 + l * 8 + k] = o[k];
   }
   __syncthreads();
-  // ---- pass 2: one block column per lane, then quantisation (jcdctmgr.c: divisor 8 * q)
+}
+
+// pass 2 of jpeg_fdct_islow on column l of block b of ws, then the quantiser of jcdctmgr.c (divisor
+// 8 * q, q = column l of the component's table): qv[k] = the quantised coefficient of row k
+__device__ __forceinline__ void fwd_pass2_quant(const int* ws, int b, int l, const uint16_t* q, int* qv) {
+  int d[8], o[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) d[k] = ws[b * 72 + k * 8 + l];
+  fdct8<1>(d, o);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int dv = 8 * (int)q[k * 8 + l];
+    const int a = (o[k] < 0 ? -o[k] : o[k]) + (dv >> 1);
+    const int qq = a >= dv ? a / dv : 0;
+    qv[k] = o[k] < 0 ? -qq : qq;
+  }
+}
+
+template <int SUB>
+__global__ void __launch_bounds__(256) jpeg_forward_kernel(const uint8_t* __restrict__ img, JpegFwd j,
+                                                           int16_t* __restrict__ coefs) {
+  constexpr int ROWS = 8 * SUB;  // pixel rows of the tile
+  constexpr int G = SUB == 2 ? 4 : 8;  // MCUs of the tile
+  __shared__ __attribute__((aligned(16))) uint8_t raw[16 * kRawPitch];
+  __shared__ __attribute__((aligned(16))) uint8_t pl[3][16][64];
+  __shared__ int ws[kFwdBlocks * 72];  // pass-1 output
+  __shared__ __attribute__((aligned(16))) int16_t outc[kFwdBlocks * 64];
+  __shared__ uint16_t qd[3][64];
+  const int t = threadIdx.x;
+  const int tx = blockIdx.x, my = blockIdx.y;
+  if (t < 192) qd[t >> 6][t & 63] = j.qt[t >> 6][t & 63];
+  const int b = t >> 3, l = t & 7;
+  int c = 0, row0 = 0, col0 = 0;
+  fwd_tile_pass1<SUB>(img, j.width, j.height, j.bgr, tx * 64, my * ROWS, raw, pl, ws, c, row0, col0);
+  // ---- pass 2: one block column per lane, then quantisation
   if (b < kFwdBlocks) {
-    int d[8], o[8];
+    int qv[8];
+    fwd_pass2_quant(ws, b, l, qd[c], qv);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) d[k] = ws[b * 72 + k * 8 + l];
-    fdct8<1>(d, o);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int dv = 8 * (int)qd[c][k * 8 + l];
-      const int a = (o[k] < 0 ? -o[k] : o[k]) + (dv >> 1);
-      const int q = a >= dv ? a / dv : 0;
-      outc[b * 64 + k * 8 + l] = (int16_t)(o[k] < 0 ? -q : q);
-    }
+    for (int k = 0; k < 8; ++k) outc[b * 64 + k * 8 + l] = (int16_t)qv[k];
   }
   __syncthreads();
   // ---- dummy luma blocks of an edge MCU (jccoefct.c compress_data): AC zero, DC of the block
@@ -716,6 +739,115 @@ __global__ void __launch_bounds__(256) jpeg_forward_kernel(const uint8_t* __rest
     if (bx < j.bw[c])
       *(uint4*)(coefs + j.coef_off[c] + ((int64_t)by * j.bw[c] + bx) * 64 + l * 8) = *(const uint4*)&outc[b * 64 + l * 8];
   }
+}
+
+// ---------------------------------------------------------------- compress + decompress round trip
+// JPEG compression as a corruption (mx_corrupt_jpeg_u8): the pixels a decoder gives back for the file
+// the encoder above would write, for a batch of images of one size, without the file and without the
+// coefficients ever leaving the workgroup.
+//   jpeg_roundtrip_kernel  the forward kernel's tile (64 pixels x one MCU row; blockIdx.z = slot of
+//                          the launch's image table) through fwd_tile_pass1 and fwd_pass2_quant; the
+//                          lane that quantised column l of a block dequantises it (coef * q) and runs
+//                          pass 1 of jpeg_idct_islow on that same column in registers, pass 2 goes by
+//                          rows through the LDS words the forward DCT used, and the range-limited
+//                          samples are stored to the image's component planes (JpegDev's layout: the
+//                          MCU-padded planes jpeg_idct_kernel writes). The dummy blocks of an edge MCU
+//                          get whatever the replicated tile gives: no decoder output reads them.
+//   jpeg_planes_rgb_kernel jpeg_colour_kernel over the planes of every image of the table.
+// The quantisation tables are scaled in the kernel from the image's quality exactly as
+// mx_jpeg_encode_info scales them (jpeg_quality_scaling, force_baseline).
+constexpr int kRtBatch = 64;  // images per launch: one table of (image, quality) pairs in the arguments
+
+struct JpegRt {
+  int32_t width, height, bgr;
+  int32_t bw[3];
+  int64_t plane_off[3];
+  int64_t plane_bytes;  // component planes of one image
+  uint8_t base[2][64];  // Annex K tables, natural order
+  int32_t image[kRtBatch], quality[kRtBatch];
+};
+
+struct JpegRtColour {
+  int32_t width, height, bgr, hs, vs;
+  int32_t bw[3], dw[3], dh[3];
+  int64_t plane_off[3];
+  int64_t plane_bytes;
+  int32_t image[kRtBatch];
+};
+
+template <int SUB>
+__global__ void __launch_bounds__(256) jpeg_roundtrip_kernel(const uint8_t* __restrict__ img, JpegRt j,
+                                                             uint8_t* __restrict__ planes) {
+  constexpr int ROWS = 8 * SUB;
+  __shared__ __attribute__((aligned(16))) uint8_t raw[16 * kRawPitch];
+  __shared__ __attribute__((aligned(16))) uint8_t pl[3][16][64];
+  __shared__ __attribute__((aligned(16))) int ws[kFwdBlocks * 72];
+  __shared__ uint16_t qd[2][64];  // luma, chroma
+  const int t = threadIdx.x;
+  const int tx = blockIdx.x, my = blockIdx.y;
+  const int64_t image = j.image[blockIdx.z];
+  if (t < 128) {
+    const int quality = j.quality[blockIdx.z];
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    const int q = ((int)j.base[t >> 6][t & 63] * scale + 50) / 100;
+    qd[t >> 6][t & 63] = (uint16_t)(q < 1 ? 1 : (q > 255 ? 255 : q));
+  }
+  const int b = t >> 3, l = t & 7;
+  int c = 0, row0 = 0, col0 = 0;
+  fwd_tile_pass1<SUB>(img + image * ((int64_t)j.width * j.height * 3), j.width, j.height, j.bgr, tx * 64, my * ROWS, raw,
+                      pl, ws, c, row0, col0);
+  int* wsb = &ws[b * 72];
+  if (b < kFwdBlocks) {
+    // forward pass 2 + quantiser, then DEQUANTIZE and pass 1 of jpeg_idct_islow, all on column l
+    const uint16_t* q = qd[c != 0];
+    int qv[8];
+    fwd_pass2_quant(ws, b, l, q, qv);
+    int64_t in[8], o[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) in[r] = (int64_t)qv[r] * q[r * 8 + l];
+    idct8(in, o);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) wsb[r * 8 + l] = (int32_t)descale(o[r], 11);
+  }
+  __syncthreads();
+  if (b < kFwdBlocks) {  // pass 2: row l, descaled by CONST_BITS + PASS1_BITS + 3, range-limited
+    int64_t in[8], o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) in[e] = (int64_t)wsb[l * 8 + e];
+    idct8(in, o);
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      lo |= (uint32_t)idct_limit(descale(o[e], 18)) << (8 * e);
+      hi |= (uint32_t)idct_limit(descale(o[e + 4], 18)) << (8 * e);
+    }
+    const int by = SUB == 2 && c == 0 ? 2 * my + (row0 >> 3) : my;
+    const int bx = (SUB == 2 && c != 0 ? tx * 4 : tx * 8) + (col0 >> 3);
+    const int bwc = sel3(j.bw, c);
+    if (bx < bwc) {
+      const int64_t off = c == 0 ? j.plane_off[0] : (c == 1 ? j.plane_off[1] : j.plane_off[2]);
+      *(uint2*)(planes + image * j.plane_bytes + off + ((int64_t)by * 8 + l) * bwc * 8 + bx * 8) = make_uint2(lo, hi);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) jpeg_planes_rgb_kernel(const uint8_t* __restrict__ planes, JpegRtColour j,
+                                                              uint8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t np = (int64_t)j.width * j.height;
+  if (i >= np) return;
+  const int64_t image = j.image[blockIdx.y];
+  const uint8_t* p = planes + image * j.plane_bytes;
+  const int x = (int)(i % j.width), y = (int)(i / j.width);
+  const int Y = p[j.plane_off[0] + (int64_t)y * j.bw[0] * 8 + x];
+  const int cb = chroma(p + j.plane_off[1], (int64_t)j.bw[1] * 8, j.hs, j.vs, j.dw[1], j.dh[1], x, y);
+  const int cr = chroma(p + j.plane_off[2], (int64_t)j.bw[2] * 8, j.hs, j.vs, j.dw[2], j.dh[2], x, y);
+  int R, G, B;
+  ycc_rgb(Y, cb, cr, R, G, B);
+  uint8_t* o = out + (image * np + i) * 3;
+  o[0] = (uint8_t)(j.bgr ? B : R);
+  o[1] = (uint8_t)G;
+  o[2] = (uint8_t)(j.bgr ? R : B);
 }
 
 // ---------------------------------------------------------------- entropy coder
@@ -1090,6 +1222,90 @@ extern "C" int mx_jpeg_forward(const uint8_t* img, int bgr, const mx_jpeg_info* 
   if (sub == 2) jpeg_forward_kernel<2><<<grid, 256, 0, st>>>(img, j, coefs);
   else jpeg_forward_kernel<1><<<grid, 256, 0, st>>>(img, j, coefs);
   MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+namespace mx {
+const uint8_t* jpeg_base_quant(int t);  // mx_jpeg.cpp
+
+// geometry of a B x H x W round trip (the layout mx_jpeg_encode_info gives one image); nullptr when fine
+static const char* roundtrip_geom(int64_t B, int64_t H, int64_t W, int subsampling, mx_jpeg_info* info, JpegDev* j,
+                                  int64_t* plane_bytes) {
+  if (B < 0 || B > INT32_MAX || H < 1 || W < 1) return "bad shape";
+  if (subsampling != 0 && subsampling != 2) return "subsampling 0 (4:4:4) or 2 (4:2:0) only";
+  if (H > 65535 || W > 65535 || H * W > ((int64_t)1 << 28)) return "image larger than 65535 a side or 2^28 pixels";
+  if (mx_jpeg_encode_info((int)W, (int)H, 50, subsampling, info) != MX_OK) return "no encoder geometry for this size";
+  to_dev(info, j, plane_bytes);
+  return nullptr;
+}
+}  // namespace mx
+
+extern "C" size_t mx_corrupt_jpeg_workspace(int64_t B, int64_t H, int64_t W, int subsampling) {
+  mx_jpeg_info info;
+  JpegDev j;
+  int64_t per = 0;
+  if (roundtrip_geom(B, H, W, subsampling, &info, &j, &per)) return 0;
+  return (size_t)(per * B);
+}
+
+extern "C" int mx_corrupt_jpeg_u8(const uint8_t* img, int64_t B, int64_t H, int64_t W, const int32_t* quality_host,
+                                  int subsampling, int bgr, void* ws, size_t ws_bytes, uint8_t* out, mx_stream_t stream) {
+  MX_CHECK_ARG(img && quality_host && out, "corrupt_jpeg_u8: null argument");
+  mx_jpeg_info info;
+  JpegDev d;
+  int64_t per = 0;
+  const char* bad = roundtrip_geom(B, H, W, subsampling, &info, &d, &per);
+  MX_CHECK_ARG(!bad, "corrupt_jpeg_u8: %s", bad);
+  const int64_t img_bytes = H * W * 3;
+  MX_CHECK_ARG(out != img, "corrupt_jpeg_u8: out must not be img");
+  MX_CHECK_ARG((uintptr_t)out + B * img_bytes <= (uintptr_t)img || (uintptr_t)img + B * img_bytes <= (uintptr_t)out,
+               "corrupt_jpeg_u8: out must not overlap img");
+  int64_t active = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    MX_CHECK_ARG(quality_host[b] >= 0 && quality_host[b] <= 100,
+                 "corrupt_jpeg_u8: quality %d of image %lld is not 1..100 (or 0: leave the image alone)",
+                 (int)quality_host[b], (long long)b);
+    active += quality_host[b] != 0;
+  }
+  if (active == 0) return MX_OK;
+  MX_CHECK_ARG(ws && (int64_t)ws_bytes >= per * B, "corrupt_jpeg_u8: workspace of %lld bytes required",
+               (long long)(per * B));
+  MX_CHECK_ARG(((uintptr_t)ws & 7) == 0, "corrupt_jpeg_u8: workspace must be 8-byte aligned");
+  const int sub = subsampling == 2 ? 2 : 1;
+  JpegRt j = {};
+  JpegRtColour k = {};
+  j.width = k.width = (int32_t)W;
+  j.height = k.height = (int32_t)H;
+  j.bgr = k.bgr = bgr ? 1 : 0;
+  j.plane_bytes = k.plane_bytes = per;
+  k.hs = d.hmax / d.h[1];
+  k.vs = d.vmax / d.v[1];
+  for (int c = 0; c < 3; ++c) {
+    j.bw[c] = k.bw[c] = d.bw[c];
+    j.plane_off[c] = k.plane_off[c] = d.plane_off[c];
+    k.dw[c] = d.dw[c];
+    k.dh[c] = d.dh[c];
+  }
+  for (int t = 0; t < 2; ++t)
+    for (int e = 0; e < 64; ++e) j.base[t][e] = jpeg_base_quant(t)[e];
+  hipStream_t st = (hipStream_t)stream;
+  int64_t b = 0;
+  while (b < B) {
+    int n = 0;
+    for (; b < B && n < kRtBatch; ++b)
+      if (quality_host[b] != 0) {
+        j.image[n] = k.image[n] = (int32_t)b;
+        j.quality[n] = quality_host[b];
+        ++n;
+      }
+    if (n == 0) break;
+    const dim3 grid((unsigned)cdiv(info.mcux, sub == 2 ? 4 : 8), (unsigned)info.mcuy, (unsigned)n);
+    if (sub == 2) jpeg_roundtrip_kernel<2><<<grid, 256, 0, st>>>(img, j, (uint8_t*)ws);
+    else jpeg_roundtrip_kernel<1><<<grid, 256, 0, st>>>(img, j, (uint8_t*)ws);
+    MX_LAUNCH_CHECK();
+    jpeg_planes_rgb_kernel<<<dim3((unsigned)cdiv(W * H, 256), (unsigned)n), 256, 0, st>>>((const uint8_t*)ws, k, out);
+    MX_LAUNCH_CHECK();
+  }
   return MX_OK;
 }
 

@@ -133,6 +133,8 @@ _SIGS = {
     "mx_jpeg_forward": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
     "mx_jpeg_entropy_workspace": (c_sz, [c_vp]),
     "mx_jpeg_entropy": (c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_i64, c_vp, c_vp]),
+    "mx_corrupt_jpeg_workspace": (c_sz, [c_i64, c_i64, c_i64, c_int]),
+    "mx_corrupt_jpeg_u8": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_vp, c_sz, c_vp, c_vp]),
     "mx_conv_set_wgrad_variant": (c_int, [c_int]),
     "mx_conv_get_wgrad_variant": (c_int, []),
     "mx_conv_set_wgrad_target": (c_int, [c_i64]),

@@ -21,6 +21,51 @@ NOISE_SIGMA = 15
 BLUR_KERNEL = 9
 BLUR_ANGLE_DEG = 0
 DOWNSCALE_FACTOR = 0.5
+JPEG_QUALITY = 15  # ImageNet-C's middle severity of its JPEG corruption; a constant of this project
+JPEG_SUBSAMPLING = 2  # 4:2:0, PIL's default for that quality
+
+DEFAULT_KINDS = ("noise", "blur", "lowres")  # the reference's corruptions
+KINDS = DEFAULT_KINDS + ("jpeg",)
+
+
+def check_kinds(kinds):
+    """kinds as a tuple; ValueError for an empty choice or a name that is no corruption."""
+    kinds = tuple(kinds)
+    bad = [k for k in kinds if k not in KINDS]
+    if bad or not kinds:
+        raise ValueError(f"corruption kinds must be a non-empty choice of {', '.join(KINDS)}; got {list(kinds)}")
+    return kinds
+
+
+def env_kinds(value=None):
+    """The corruption kinds of a training run: `value`, or MX_CORRUPTIONS, a comma-separated list
+    (default noise,blur,lowres)."""
+    import os
+    value = os.environ.get("MX_CORRUPTIONS", "") if value is None else value
+    if isinstance(value, str):
+        value = [k.strip() for k in value.split(",") if k.strip()] or DEFAULT_KINDS
+    return check_kinds(value)
+
+
+EXTRA_VARIANTS = {"jpeg": ("Test_JPEG", "JPEG")}  # name -> (test-set variant, its short name)
+
+
+def env_extra_variants(value=None):
+    """Test-set variants beyond the reference's four, as [(variant, short name)]: `value`, or
+    MX_EXTRA_VARIANTS, a comma-separated list (default empty; jpeg is the only name)."""
+    import os
+    value = os.environ.get("MX_EXTRA_VARIANTS", "") if value is None else value
+    names = [k.strip() for k in value.split(",") if k.strip()] if isinstance(value, str) else list(value)
+    bad = [k for k in names if k not in EXTRA_VARIANTS]
+    if bad:
+        raise ValueError(f"MX_EXTRA_VARIANTS names {', '.join(EXTRA_VARIANTS)} only; got {bad}")
+    return [EXTRA_VARIANTS[k] for k in dict.fromkeys(names)]
+
+
+def _choice(kinds):
+    """The reference's draw for its three kinds (the same call, so the same `random` stream), a uniform
+    choice of the given ones otherwise."""
+    return random.choice(["noise", "blur", "lowres"]) if tuple(kinds) == DEFAULT_KINDS else random.choice(list(kinds))
 
 
 def _dev():
@@ -106,45 +151,58 @@ def apply_lowres(img_bgr: np.ndarray, factor: float) -> np.ndarray:
     return _run(img_bgr, ops.CORRUPT_LOWRES, factor=float(factor))
 
 
-def _apply_random_corruption(img_bgr: np.ndarray) -> np.ndarray:
-    choice = random.choice(["noise", "blur", "lowres"])
+def apply_jpeg(img_bgr: np.ndarray, quality: int) -> np.ndarray:
+    """The BGR pixels a decoder reads back from img_bgr saved as JPEG at `quality` (4:2:0)."""
+    t = torch.from_numpy(np.ascontiguousarray(img_bgr, dtype=np.uint8))[None].to(_dev())
+    return ops.corrupt_jpeg_u8(t, int(quality), JPEG_SUBSAMPLING, bgr=True)[0].cpu().numpy()
+
+
+def _apply_random_corruption(img_bgr: np.ndarray, kinds=DEFAULT_KINDS) -> np.ndarray:
+    choice = _choice(kinds)
     if choice == "noise":
         return apply_noise(img_bgr, NOISE_SIGMA)
     if choice == "blur":
         return apply_motion_blur(img_bgr, BLUR_KERNEL, BLUR_ANGLE_DEG)
+    if choice == "jpeg":
+        return apply_jpeg(img_bgr, JPEG_QUALITY)
     return apply_lowres(img_bgr, DOWNSCALE_FACTOR)
 
 
 class RandomCorruption:
-    """PIL transform: with probability p apply one random corruption (augmentations.py:60-74)."""
+    """PIL transform: with probability p apply one random corruption (augmentations.py:60-74), drawn
+    from `kinds` (the reference's three by default; "jpeg" may join them)."""
 
-    def __init__(self, p: float = 0.5):
+    def __init__(self, p: float = 0.5, kinds=DEFAULT_KINDS):
         self.p = p
+        self.kinds = check_kinds(kinds)
 
     def __call__(self, img):
         from PIL import Image
         if random.random() > self.p:
             return img
         bgr = np.ascontiguousarray(np.asarray(img)[..., ::-1])  # cv2.cvtColor(RGB2BGR)
-        out = _apply_random_corruption(bgr)
+        out = _apply_random_corruption(bgr, self.kinds)
         return Image.fromarray(np.ascontiguousarray(out[..., ::-1]))  # BGR2RGB
 
 
 class RandomCorruptionGPU:
     """Device form for uint8 HWC tensors: same decision rule (keep with prob 1-p, else a uniform choice
-    of noise / blur / lowres) drawn from Python's `random` like the reference; noise from Philox."""
+    of `kinds`: noise / blur / lowres by default) drawn from Python's `random` like the reference; noise
+    from Philox. The images are RGB here, so a "jpeg" draw compresses them as RGB."""
 
-    CODES = {"noise": ops.CORRUPT_NOISE, "blur": ops.CORRUPT_BLUR, "lowres": ops.CORRUPT_LOWRES}
+    CODES = {"noise": ops.CORRUPT_NOISE, "blur": ops.CORRUPT_BLUR, "lowres": ops.CORRUPT_LOWRES,
+             "jpeg": ops.CORRUPT_JPEG}
 
-    def __init__(self, p: float = 0.5):
+    def __init__(self, p: float = 0.5, kinds=DEFAULT_KINDS):
         self.p = p
+        self.kinds = check_kinds(kinds)
 
     def __call__(self, img):
         if random.random() > self.p:
             return img
-        code = self.CODES[random.choice(["noise", "blur", "lowres"])]
+        code = self.CODES[_choice(self.kinds)]
         return ops.corrupt_u8(img[None], [code], sigma=NOISE_SIGMA, seed=random.getrandbits(63),
-                              factor=DOWNSCALE_FACTOR)[0]
+                              factor=DOWNSCALE_FACTOR, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING)[0]
 
 
 def patch_ultralytics_augmentations():

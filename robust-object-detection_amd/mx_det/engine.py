@@ -211,9 +211,10 @@ def evaluate(model, loader, ann_file, dev, per_class=False, device_eval=None):
 
 def train_frcnn(cfg):
     """cfg: dict with SEED, EPOCHS, BATCH_SIZE, LR, WEIGHT_DECAY, MOMENTUM, TRAIN_IMG, TRAIN_ANN, VAL_IMG,
-    VAL_ANN, OUT_DIR, AUGMENT (bool), optional WEIGHTS (checkpoint path), NUM_WORKERS."""
+    VAL_ANN, OUT_DIR, AUGMENT (bool), optional WEIGHTS (checkpoint path), NUM_WORKERS, CORRUPTIONS (the
+    kinds AUGMENT draws from: a list or comma-separated string, else MX_CORRUPTIONS, else noise,blur,lowres)."""
     from .dataset import COCODetectionDataset, collate_fn, uint8_transform
-    from .augment import RandomCorruptionGPU
+    from .augment import RandomCorruptionGPU, env_kinds
 
     set_seed(cfg["SEED"])
     dev, world, rank = init_device()
@@ -265,7 +266,9 @@ def train_frcnn(cfg):
     optimizer = SGD(params, lr=lr, momentum=cfg["MOMENTUM"], weight_decay=cfg["WEIGHT_DECAY"])
     sched = torch.optim.lr_scheduler.StepLR(optimizer, step_size=8, gamma=0.1)
     it_global = 0
-    corrupt = RandomCorruptionGPU(p=0.5) if cfg.get("AUGMENT") else None
+    # cfg CORRUPTIONS / MX_CORRUPTIONS: the kinds an augmented run draws from (default: the reference's)
+    kinds = env_kinds(cfg.get("CORRUPTIONS"))
+    corrupt = RandomCorruptionGPU(p=0.5, kinds=kinds) if cfg.get("AUGMENT") else None
     history, best_ckpt, last_ckpt = out_dir / "history.jsonl", out_dir / "best.pth", out_dir / "last.pth"
     t0 = time.time()
     # cfg["TIMER"] = {"warmup": W}: bench.py --mode script's clock -- after W optimizer steps the device

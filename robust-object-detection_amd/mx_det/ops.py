@@ -644,23 +644,60 @@ def detections_postprocess(logits, reg, rois, img, hw, N, score_thresh, nms_thre
 
 # ---------------------------------------------------------------------------------------------
 CORRUPT_NONE, CORRUPT_NOISE, CORRUPT_BLUR, CORRUPT_LOWRES = 0, 1, 2, 3
+CORRUPT_JPEG = 4  # not an mx_corrupt_u8 op: corrupt_u8 hands these images to mx_corrupt_jpeg_u8
 
 
-def corrupt_u8(images, ops, sigma=15.0, seed=0, noise=None, factor=0.5):
-    """augmentations.py corruption ops on uint8 [B,H,W,C] (one op code per image)."""
+def corrupt_jpeg_u8(images, quality, subsampling=2, bgr=False, out=None):
+    """JPEG compression as a corruption on uint8 [B,H,W,3]: out[b] = the pixels PIL reads back from
+    images[b] saved as JPEG at that quality and subsampling (0 = 4:4:4, 2 = 4:2:0), bit for bit
+    (mx_corrupt_jpeg_u8: two launches for the batch, no file, no host synchronisation). quality: one
+    int in 1..100, or one per image, where 0 leaves out[b] as it is (images[b] when out is None).
+    bgr: images and out are BGR. out: a contiguous uint8 tensor like images, not images itself."""
+    _dev(images)
+    _check(images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3, "images must be uint8 [B,H,W,3]")
+    x = images.contiguous()
+    B, H, W, _ = x.shape
+    q = [int(quality)] * B if isinstance(quality, int) else [int(v) for v in quality]
+    _check(len(q) == B, "corrupt_jpeg_u8: one quality, or one per image")
+    if isinstance(quality, int):
+        _check(1 <= q[0] <= 100 if B else True, "corrupt_jpeg_u8: quality must be 1..100")
+    if out is None:
+        out = x.clone() if 0 in q else torch.empty_like(x)
+    else:
+        _check(torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == x.device and out.shape == x.shape
+               and out.is_contiguous(), "corrupt_jpeg_u8: out must be a contiguous uint8 tensor like images")
+    if B == 0:
+        return out
+    nbytes = _lib.load().mx_corrupt_jpeg_workspace(B, H, W, int(subsampling))
+    ws = _ws(nbytes, x.device)
+    call("mx_corrupt_jpeg_u8", _p(x), B, H, W, (ctypes.c_int32 * B)(*q), int(subsampling), int(bool(bgr)), _p(ws),
+         int(nbytes), _p(out), _stream())
+    return out
+
+
+def corrupt_u8(images, ops, sigma=15.0, seed=0, noise=None, factor=0.5, quality=15, subsampling=2, bgr=False):
+    """augmentations.py corruption ops on uint8 [B,H,W,C] (one op code per image). CORRUPT_JPEG images
+    are compressed at `quality` / `subsampling` (bgr: the images are BGR) by one corrupt_jpeg_u8 call
+    behind the others' launches; a batch without that code makes the single mx_corrupt_u8 call."""
     _dev(images)
     _check(images.dtype == torch.uint8 and images.dim() == 4, "images must be uint8 [B,H,W,C]")
     x = images.contiguous()
     B, H, W, C = x.shape
+    codes = [int(o) for o in ops]
+    jpeg = [o == CORRUPT_JPEG for o in codes]
     out = torch.empty_like(x)
     nw, nh = max(1, int(W * factor)), max(1, int(H * factor))
-    tmp = torch.empty((B, nh, nw, C), dtype=torch.uint8, device=x.device) if 3 in list(ops) else None
+    tmp = torch.empty((B, nh, nw, C), dtype=torch.uint8, device=x.device) if 3 in codes else None
     if noise is not None:
         noise = noise.float().contiguous()
         _check(noise.numel() == x.numel(), "noise field must match images")
-    arr = (ctypes.c_int32 * B)(*[int(o) for o in ops])
+    arr = (ctypes.c_int32 * B)(*[CORRUPT_NONE if j else o for o, j in zip(codes, jpeg)])
     call("mx_corrupt_u8", _p(x), B, H, W, C, arr, float(sigma), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
          _p(noise), float(factor), _p(tmp), _p(out), _stream())
+    if any(jpeg):
+        _check(C == 3, "corrupt_u8: JPEG compression takes 3-channel images")
+        _check(1 <= int(quality) <= 100, "corrupt_u8: quality must be 1..100")
+        corrupt_jpeg_u8(x, [int(quality) if j else 0 for j in jpeg], subsampling, bgr, out=out)
     return out
 
 

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import augment, ops
 
 NOISE, BLUR, LOWRES = ops.CORRUPT_NOISE, ops.CORRUPT_BLUR, ops.CORRUPT_LOWRES  # augmentations.py ops
 
@@ -355,15 +355,21 @@ class DevicePatchLoader:
 
 class RestorationBatcher:
     """uint8 clean patches [B,S,S,3] (host) -> (corrupted, clean) f32 NCHW in [0, 1] on the device;
-    each patch gets random.choice(noise, blur, lowres) as in _apply_random_corruption (:92-100)."""
+    each patch gets random.choice(noise, blur, lowres) as in _apply_random_corruption (:92-100), or a
+    uniform choice of `kinds` when those are given ("jpeg": compression at augment.JPEG_QUALITY)."""
 
-    def __init__(self, dev):
+    def __init__(self, dev, kinds=augment.DEFAULT_KINDS):
         self.dev = dev
+        self.kinds = augment.check_kinds(kinds)
 
     def __call__(self, clean_u8):
         x = clean_u8.to(self.dev, non_blocking=True)
-        codes = [random.choice((NOISE, BLUR, LOWRES)) for _ in range(x.shape[0])]
-        cor = ops.corrupt_u8(x, codes, seed=random.getrandbits(62))
+        if self.kinds == augment.DEFAULT_KINDS:
+            codes = [random.choice((NOISE, BLUR, LOWRES)) for _ in range(x.shape[0])]
+        else:
+            codes = [augment.RandomCorruptionGPU.CODES[random.choice(list(self.kinds))] for _ in range(x.shape[0])]
+        cor = ops.corrupt_u8(x, codes, seed=random.getrandbits(62), quality=augment.JPEG_QUALITY,
+                             subsampling=augment.JPEG_SUBSAMPLING)
         to = lambda t: t.permute(0, 3, 1, 2).float().div_(255.0)  # noqa: E731
         return to(cor), to(x)
 

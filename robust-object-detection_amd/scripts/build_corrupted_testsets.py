@@ -14,6 +14,9 @@ cv2.imread; PIL decodes the formats it does not handle), corrupted there, and en
 (mx_det.jpeg.encode: byte-identical to PIL / libjpeg-turbo at cv2.imwrite's default quality 95), so
 only the bytes of the written file come back. MX_JPEG_ENCODE=host copies the pixels back and lets PIL
 encode them instead.
+MX_EXTRA_VARIANTS=jpeg appends Test_JPEG after the reference's four: every image compressed at
+augment.JPEG_QUALITY (4:2:0) and decoded again on the device (ops.corrupt_jpeg_u8), then written at
+quality 95 like the others. It draws nothing from np.random, so the noise fields are unchanged.
 """
 import os
 import shutil
@@ -34,7 +37,13 @@ BLUR_KERNEL = 9
 BLUR_ANGLE_DEG = 0
 DOWNSCALE_FACTOR = 0.5
 VARIANTS = ["Test_Clean", "Test_Noise", "Test_Blur", "Test_LowRes"]
+JPEG_QUALITY = augment.JPEG_QUALITY
 NAMES = ["pedestrian", "car", "van", "truck", "bus", "motor"]
+
+
+def variants():
+    """The reference's four variants, then those MX_EXTRA_VARIANTS names."""
+    return VARIANTS + [v for v, _ in augment.env_extra_variants()]
 
 
 def set_seed(seed):
@@ -55,6 +64,8 @@ def corrupt(img_bgr, variant):
             return augment.apply_motion_blur(img_bgr, BLUR_KERNEL, BLUR_ANGLE_DEG)
         if variant == "Test_LowRes":
             return augment.apply_lowres(img_bgr, DOWNSCALE_FACTOR)
+        if variant == "Test_JPEG":
+            return augment.apply_jpeg(img_bgr, JPEG_QUALITY)
         return img_bgr
     x = img_bgr[None]
     if variant == "Test_Noise":  # the reference's numpy stream, added / clipped / truncated on the device
@@ -65,6 +76,8 @@ def corrupt(img_bgr, variant):
         return ops.filter2d_u8(x, taps)[0]
     if variant == "Test_LowRes":
         return ops.corrupt_u8(x, [ops.CORRUPT_LOWRES], factor=float(DOWNSCALE_FACTOR))[0]
+    if variant == "Test_JPEG":
+        return ops.corrupt_jpeg_u8(x, JPEG_QUALITY, bgr=True)[0]
     return img_bgr
 
 
@@ -115,7 +128,7 @@ def build_yolo_testsets(src=None, out_root=None):
     src_img_dir, src_lbl_dir = src / "images" / "val", src / "labels" / "val"
     if not src_img_dir.exists() or not src_lbl_dir.exists():
         raise FileNotFoundError("YOLO val images/labels not found. Check YOLO_SRC path.")
-    for v in VARIANTS:
+    for v in variants():
         dst_root = out_root / "yolo6" / v
         dst_img_dir, dst_lbl_dir = dst_root / "images" / "val", dst_root / "labels" / "val"
         ensure_dir(dst_img_dir)
@@ -132,7 +145,7 @@ def build_coco_testsets(src=None, out_root=None):
     src_img_dir, src_ann = src / "images" / "val", src / "annotations" / "instances_val.json"
     if not src_img_dir.exists() or not src_ann.exists():
         raise FileNotFoundError("COCO val images or instances_val.json not found. Check COCO_SRC path.")
-    for v in VARIANTS:
+    for v in variants():
         dst_root = out_root / "coco6" / v
         dst_img_dir, dst_ann_dir = dst_root / "images" / "val", dst_root / "annotations"
         ensure_dir(dst_img_dir)

@@ -5,6 +5,7 @@ FRCNN branch of the reference's eval_all.py (:79-156, :198-213) on MI355X; the U
 YOLO branches are outside this build's scope and are reported as skipped.
 Outputs keep the reference schema: experiments/eval_results.json ({model: {variant: {mAP50_95, mAP50,
 per_class_ap50}}}) and experiments/eval_results.csv. torchrun shards the images per rank.
+MX_EXTRA_VARIANTS=jpeg adds the Test_JPEG set (column JPEG) after the reference's four.
 """
 import csv
 import json
@@ -13,6 +14,7 @@ from pathlib import Path
 
 import torch
 
+from mx_det.augment import EXTRA_VARIANTS, env_extra_variants
 from mx_det.engine import dist_info, eval_frcnn_variant, init_device, load_frcnn_checkpoint
 
 VARIANTS = ["Test_Clean", "Test_Noise", "Test_Blur", "Test_LowRes"]
@@ -28,6 +30,15 @@ BASELINE_PAIRS = [("FasterRCNN", "FasterRCNN_aug"), ("RT-DETR-L", "RT-DETR-L_aug
 OUT_DIR = Path("experiments")
 
 
+def all_variants():
+    """The reference's four variants, then those MX_EXTRA_VARIANTS names."""
+    return VARIANTS + [v for v, _ in env_extra_variants()]
+
+
+def short(v):
+    return SHORT[v] if v in SHORT else dict(EXTRA_VARIANTS.values())[v]
+
+
 def variant_paths(root, v):
     return str(root / v / "images" / "val"), str(root / v / "annotations" / "instances_val.json")
 
@@ -35,7 +46,7 @@ def variant_paths(root, v):
 def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None):
     rank = dist_info()[1]
     root = COCO_TESTSET_ROOT if root is None else root
-    variants = VARIANTS if variants is None else variants
+    variants = all_variants() if variants is None else variants
     if rank == 0:
         print("=" * 60 + f"\n  {name}  (COCOeval bbox)\n" + "=" * 60, flush=True)
     model = load_frcnn_checkpoint(ckpt, dev)
@@ -45,7 +56,7 @@ def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None):
         m = eval_frcnn_variant(model, img_dir, ann, dev, restorer=restorer if v != "Test_Clean" else None)
         if rank == 0:
             res[v] = m
-            print(f"  [{SHORT[v]}] mAP50={m['mAP50']:.4f}  mAP50-95={m['mAP50_95']:.4f}", flush=True)
+            print(f"  [{short(v)}] mAP50={m['mAP50']:.4f}  mAP50-95={m['mAP50_95']:.4f}", flush=True)
     del model
     torch.cuda.empty_cache()
     return res
@@ -58,23 +69,23 @@ def save_json(all_results, path):
 
 
 def save_csv(all_results, path, variants=None, pairs=None):
-    variants = VARIANTS if variants is None else variants
+    variants = all_variants() if variants is None else variants
     pairs = BASELINE_PAIRS if pairs is None else pairs
     models = [m for m in MODEL_ORDER if m in all_results]
     with open(path, "w", newline="", encoding="utf-8") as f:
         w = csv.writer(f)
-        w.writerow(["Model", "Metric"] + [SHORT[v] for v in variants])
+        w.writerow(["Model", "Metric"] + [short(v) for v in variants])
         for m in models:
             w.writerow([m, "mAP@50"] + [f"{all_results[m][v]['mAP50']:.4f}" for v in variants])
             w.writerow([m, "mAP@50-95"] + [f"{all_results[m][v]['mAP50_95']:.4f}" for v in variants])
         w.writerow([])
-        w.writerow(["Model", "Metric"] + [SHORT[v] for v in variants[1:]])
+        w.writerow(["Model", "Metric"] + [short(v) for v in variants[1:]])
         for m in models:
             clean = all_results[m]["Test_Clean"]["mAP50"]
             w.writerow([m, "Deg%_mAP50"] + [f"{((all_results[m][v]['mAP50'] - clean) / clean * 100 if clean > 0 else 0.0):.1f}%"
                                             for v in variants[1:]])
         w.writerow([])
-        w.writerow(["Model", "Metric"] + [SHORT[v] for v in variants])
+        w.writerow(["Model", "Metric"] + [short(v) for v in variants])
         for base, aug in pairs:
             if base in all_results and aug in all_results:
                 w.writerow([base, "Aug-Base_mAP50"] + [f"{all_results[aug][v]['mAP50'] - all_results[base][v]['mAP50']:+.4f}"

@@ -6,6 +6,7 @@ do the JPEG decode (mx_det.jpeg.read_file; PIL for the files it does not handle)
 encode (mx_det.jpeg.write_file), both bit-identical to libjpeg-turbo: pixels never visit the host.
 MX_JPEG_ENCODE=host encodes with PIL instead; MX_JPEG_DECODE=device decodes the scan on the device
 too (the default decodes it on the host). The fused eval path (eval_restored.py) skips this step.
+MX_EXTRA_VARIANTS=jpeg restores Test_JPEG as well.
 """
 import os
 import shutil
@@ -17,11 +18,17 @@ from PIL import Image
 
 from scripts import eval_restored
 from mx_det import jpeg
+from mx_det.augment import env_extra_variants
 from mx_det.engine import init_device
 
 COCO_TESTSET_ROOT = Path("data/testsets/coco6")
 COCO_OUT_ROOT = Path("data/testsets/coco6_restored")
 VARIANTS_TO_RESTORE = ["Test_Noise", "Test_Blur", "Test_LowRes"]
+
+
+def variants_to_restore():
+    """The reference's three corrupted variants, then those MX_EXTRA_VARIANTS names."""
+    return VARIANTS_TO_RESTORE + [v for v, _ in env_extra_variants()]
 
 
 def read_rgb(path, dev):
@@ -60,7 +67,7 @@ def restore_variant(unet, variant, dev, src_root=None, dst_root=None):
 def main():
     dev, _, _ = init_device()
     unet = eval_restored.load_unet(dev)
-    for v in VARIANTS_TO_RESTORE:
+    for v in variants_to_restore():
         restore_variant(unet, v, dev)
     clean_src, clean_dst = COCO_TESTSET_ROOT / "Test_Clean", COCO_OUT_ROOT / "Test_Clean"
     if clean_src.exists() and not clean_dst.exists():
