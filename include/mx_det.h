@@ -258,6 +258,35 @@ int mx_corrupt_u8(const uint8_t* img, int64_t B, int64_t H, int64_t W, int64_t C
  * Low-res (op 3) takes OpenCV's exact-x2 INTER_AREA fast path when W == 2*nw and H == 2*nh. */
 int mx_filter2d_u8(const uint8_t* img, int64_t B, int64_t H, int64_t W, int64_t C, const float* taps_host, int ntaps,
                    uint8_t* out, mx_stream_t stream);
+/* The corruptions for a whole batch in one launch, each image with its own op, strength and size
+ * (severity sweeps, severity-randomised augmentation, a list of detection frames of any sizes).
+ * One descriptor per image, in a host array: */
+typedef struct mx_corrupt_desc {
+  const uint8_t* src; /* device, u8 [H][W][3] */
+  uint8_t* dst;       /* device, u8 [H][W][3] */
+  int32_t H, W;       /* 1..32768 each */
+  int32_t op;         /* 0 none (copy), 1 noise, 2 blur, 3 low-res */
+  float sigma;        /* op 1 */
+  uint64_t seed;      /* op 1: Philox key; the counter is the element's flat index within its image */
+  int32_t tap_off, ntaps; /* op 2: this image's (dy, dx, coef) triples in the call's tap table; ntaps <= 128,
+                             |dy|, |dx| <= 15 */
+  int32_t nh, nw;     /* op 3: the low-res size, 1 <= nh <= H, 1 <= nw <= W */
+} mx_corrupt_desc;
+/* out = the same bits as mx_corrupt_u8 (ops 1, 3; op 3 takes the exact-x2 path when W == 2*nw and
+ * H == 2*nh) and mx_filter2d_u8 (op 2, any tap set within the reach) give for that image alone. taps_host:
+ * ntaps_total (dy, dx, coef) f32 triples, row-major kernel order, shared by the descriptors. noise: NULL
+ * (Philox from sigma / seed), or one f32 field on the device for the whole call: the images' [H][W][3]
+ * fields back to back in descriptor order, whatever their ops (for a [B,H,W,3] batch: [B][H][W][3]).
+ * One launch per chunk of 16 images (fewer when their distinct tap sets exceed 192 taps); descriptors
+ * and taps travel as kernel arguments: no workspace, no upload, no host synchronisation, capturable in
+ * a graph. Low-res is fused (no intermediate image). Every descriptor is checked before the first
+ * launch. src == dst is allowed for op 1 (in place) and op 0 (nothing is done), refused for ops 2, 3;
+ * src and dst ranges that overlap without being equal are refused, and so is an output that overlaps
+ * another image's input or output. */
+int mx_corrupt_batch_u8(const mx_corrupt_desc* descs_host, int64_t n, const float* taps_host, int64_t ntaps_total,
+                        const float* noise, mx_stream_t stream);
+/* out[0], out[1] = rows, columns of the output tile one workgroup of mx_corrupt_batch_u8 owns. */
+int mx_corrupt_batch_tile(int32_t out[2]);
 /* GeneralizedRCNNTransform (normalize, zero-pad to /32) fused with ToDtype(scale=True):
  * u8 HWC [B,H,W,3] -> NHWC [B, Hp, Wp, Cp] dtype, (x/255 - mean)/std, zero padding; Cp >= 3 (extra
  * channels zero, for the conv stem's 8-channel gather). */

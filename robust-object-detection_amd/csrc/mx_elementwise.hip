@@ -2,6 +2,7 @@
 // Built -ffp-contract=off: every f32 op rounds once, as the restated torch / OpenCV code does.
 #include "mx_common.h"
 #include "mx_boxcoder.h"
+#include "mx_corrupt_ops.h"
 
 namespace mx {
 
@@ -28,45 +29,14 @@ __global__ void decode_kernel(const float4* __restrict__ rel, const float4* __re
 }
 
 // ---- corruption (scripts/augmentations.py:30-45) --------------------------------------------
-// Philox4x32-10 counter RNG + Box-Muller: N(0, sigma) per element (the on-device replacement of
-// np.random.normal, which cannot be matched bit for bit; parity tests pass the field explicitly).
-__device__ __forceinline__ uint4 philox(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
-
-__device__ __forceinline__ float gauss(uint64_t seed, uint64_t idx) {
-  uint4 r = philox(make_uint4((uint32_t)idx, (uint32_t)(idx >> 32), 0x5eedu, 0u), make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-  float u1 = ((float)(r.x >> 8) + 1.0f) * (1.0f / 16777217.0f);
-  float u2 = (float)(r.y >> 8) * (1.0f / 16777216.0f);
-  return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-}
-
-// apply_noise: clip(f32(img) + f32(noise), 0, 255).astype(uint8) (truncation)
+// The per-element arithmetic (Philox noise, filter2D sum, INTER_AREA, INTER_LINEAR) is in
+// mx_corrupt_ops.h, shared with the batched kernel of mx_corrupt.hip; the kernels here are one op over
+// one image per launch, one element per thread, every source value read from global memory.
 __global__ void noise_kernel(const uint8_t* __restrict__ img, const float* __restrict__ noise, float sigma, uint64_t seed,
                              int64_t n, uint8_t* __restrict__ out) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float nz = noise ? noise[i] : sigma * gauss(seed, (uint64_t)i);
-  float v = (float)img[i] + nz;
-  v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
-  out[i] = (uint8_t)v;
-}
-
-__device__ __forceinline__ int64_t refl101(int64_t i, int64_t n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) {
-    if (i < 0) i = -i;
-    if (i >= n) i = 2 * n - 2 - i;
-  }
-  return i;
+  out[i] = noise_px([&] { return img[i]; }, noise, sigma, seed, i);
 }
 
 // filter2D with the angle-0 9x9 motion kernel: only row 4 is non-zero (float(1/9) each), so the
@@ -100,11 +70,9 @@ __global__ void filter2d_kernel(const uint8_t* __restrict__ img, int64_t H, int6
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= H * W * C) return;
   int64_t c = i % C, x = (i / C) % W, y = i / (C * W);
-  float s = 0.f;
-  for (int k = 0; k < t.n; ++k) s += t.c[k] * (float)img[(refl101(y + t.dy[k], H) * W + refl101(x + t.dx[k], W)) * C + c];
-  float r = rintf(s);
-  r = r < 0.f ? 0.f : (r > 255.f ? 255.f : r);
-  out[i] = (uint8_t)r;
+  out[i] = filter2d_px(
+      t.n, [&](int k) { return t.c[k]; },
+      [&](int k) { return img[(refl101(y + t.dy[k], H) * W + refl101(x + t.dx[k], W)) * C + c]; });
 }
 
 // INTER_AREA with an exact integer scale of 2 in both axes (OpenCV resize's is_area_fast branch,
@@ -121,31 +89,7 @@ __global__ void area_fast2_kernel(const uint8_t* __restrict__ src, int64_t sw, i
   const uint8_t* s0 = src + ((2 * dy) * sw + 2 * dx) * C + c;
   const uint8_t* s1 = s0 + sw * C;
   const int sum = (int)s0[0] + (int)s0[C] + (int)s1[0] + (int)s1[C];
-  if (e < vec_elems) {
-    dst[i] = (uint8_t)((sum + 2) >> 2);
-  } else {
-    const float r = rintf((float)sum * 0.25f);
-    dst[i] = (uint8_t)(r > 255.f ? 255.f : r);
-  }
-}
-
-// OpenCV computeResizeAreaTab for one destination index: up to 3 (src, alpha) entries
-__device__ int area_entries(int64_t ssize, int64_t d, double scale, int64_t* si, float* al) {
-  int k = 0;
-  double fs1 = d * scale, fs2 = fs1 + scale;
-  double cell = scale < (ssize - fs1) ? scale : (ssize - fs1);
-  int64_t s1 = (int64_t)ceil(fs1), s2 = (int64_t)floor(fs2);
-  if (s2 > ssize - 1) s2 = ssize - 1;
-  if (s1 > s2) s1 = s2;
-  if (s1 - fs1 > 1e-3) { si[k] = s1 - 1; al[k++] = (float)((s1 - fs1) / cell); }
-  for (int64_t s = s1; s < s2 && k < 7; ++s) { si[k] = s; al[k++] = (float)(1.0 / cell); }
-  if (fs2 - s2 > 1e-3 && k < 8) {
-    double dd = fs2 - s2;
-    if (dd > 1.) dd = 1.;
-    if (dd > cell) dd = cell;
-    si[k] = s2; al[k++] = (float)(dd / cell);
-  }
-  return k;
+  dst[i] = area_fast2_px(sum, e < vec_elems);
 }
 
 // INTER_AREA general path: out = sat(sum_y beta_y * (sum_x alpha_x * S)) in f32, same order as OpenCV
@@ -158,27 +102,7 @@ __global__ void area_kernel(const uint8_t* __restrict__ src, int64_t sh, int64_t
   float xa[8], ya[8];
   int nx = area_entries(sw, dx, (double)sw / dw, xs, xa);
   int ny = area_entries(sh, dy, (double)sh / dh, ys, ya);
-  float sum = 0.f;
-  for (int j = 0; j < ny; ++j) {
-    const uint8_t* S = src + ys[j] * sw * C;
-    float buf = 0.f;
-    for (int k = 0; k < nx; ++k) buf = buf + (float)S[xs[k] * C + c] * xa[k];
-    sum = j == 0 ? ya[j] * buf : sum + ya[j] * buf;
-  }
-  float r = rintf(sum);
-  dst[i] = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
-}
-
-__device__ __forceinline__ void lin_coef(int64_t ssize, int64_t dsize, int64_t d, int64_t* s_out, int* a0, int* a1) {
-  double scale = 1.0 / ((double)dsize / ssize);
-  float f = (float)((d + 0.5) * scale - 0.5);
-  int64_t s = (int64_t)floorf(f);
-  f -= (float)s;
-  if (s < 0) { f = 0.f; s = 0; }
-  if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
-  *s_out = s;
-  *a0 = (int)rintf((1.f - f) * 2048.f);
-  *a1 = (int)rintf(f * 2048.f);
+  dst[i] = area_px(nx, xa, ny, ya, [&](int j, int k) { return src[ys[j] * sw * C + xs[k] * C + c]; });
 }
 
 // INTER_LINEAR 8U, 11-bit fixed point; vertical combine as OpenCV's SIMD path (see oracle)
@@ -192,10 +116,8 @@ __global__ void linear_kernel(const uint8_t* __restrict__ src, int64_t sh, int64
   lin_coef(sh, dh, y, &r0, &b0, &b1);
   lin_coef(sw, dw, x, &c0, &a0, &a1);
   int64_t r1 = r0 + 1 < sh ? r0 + 1 : sh - 1, c1 = c0 + 1 < sw ? c0 + 1 : sw - 1;
-  int S0 = src[(r0 * sw + c0) * C + c] * a0 + src[(r0 * sw + c1) * C + c] * a1;
-  int S1 = src[(r1 * sw + c0) * C + c] * a0 + src[(r1 * sw + c1) * C + c] * a1;
-  int v = ((((S0 >> 4) * b0) >> 16) + (((S1 >> 4) * b1) >> 16) + 2) >> 2;
-  dst[i] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+  dst[i] = linear_px(src[(r0 * sw + c0) * C + c], src[(r0 * sw + c1) * C + c], src[(r1 * sw + c0) * C + c],
+                     src[(r1 * sw + c1) * C + c], a0, a1, b0, b1);
 }
 
 // ToDtype(float32, scale=True) -> x * float(1/255); GeneralizedRCNNTransform.normalize (x-mean)/std;
@@ -432,14 +354,6 @@ extern "C" int mx_roi_compact(const uint8_t* mask, int64_t M, int64_t K, int64_t
                                                         rois, lab_out, (float4*)tg_out);
   MX_LAUNCH_CHECK();
   return MX_OK;
-}
-
-// elements per destination row that ResizeAreaFastVec_SIMD_8u (scale 2, 128-bit vectors) handles:
-// cn 1: 8 per step, cn 3: 48 per step, cn 4: 16 per step; other channel counts: none (scalar)
-static int64_t area_fast2_vec_elems(int64_t dw, int64_t C) {
-  const int64_t w = dw * C;
-  const int64_t step = C == 1 ? 8 : (C == 3 ? 48 : (C == 4 ? 16 : 0));
-  return step ? (w / step) * step : 0;
 }
 
 extern "C" int mx_filter2d_u8(const uint8_t* img, int64_t B, int64_t H, int64_t W, int64_t C, const float* taps_host,

@@ -36,6 +36,13 @@ class ConvCfg(ctypes.Structure):
 c_cfg = ctypes.POINTER(ConvCfg)
 
 
+class CorruptDesc(ctypes.Structure):
+    """mx_corrupt_desc (include/mx_det.h): one image of an mx_corrupt_batch_u8 call."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("op", ctypes.c_int32), ("sigma", ctypes.c_float), ("seed", ctypes.c_uint64),
+                ("tap_off", ctypes.c_int32), ("ntaps", ctypes.c_int32), ("nh", ctypes.c_int32), ("nw", ctypes.c_int32)]
+
+
 class JpegInfo(ctypes.Structure):
     """mx_jpeg_info (include/mx_det.h)."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32),
@@ -93,6 +100,8 @@ _SIGS = {
                               c_vp]),
     "mx_corrupt_u8": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_f, c_u64, c_vp, c_d, c_vp, c_vp, c_vp]),
     "mx_filter2d_u8": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp]),
+    "mx_corrupt_batch_u8": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "mx_corrupt_batch_tile": (c_int, [c_vp]),
     "mx_normalize_pad": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp]),
     "mx_resize_normalize_pad": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_int,
                                         c_vp, c_vp]),

@@ -9,6 +9,10 @@ apply_noise draws its field with np.random.normal(0, sigma, shape) exactly like 
 seeded numpy stream reproduces the reference output bit for bit; the add/clip/truncate runs on
 device. RandomCorruptionGPU is the training-loop form: uint8 HWC device tensors in and out, the noise
 field from the on-device Philox generator, never leaving HBM.
+SEVERITY gives every corruption five levels (level 3 = the constants above); severity_spec / env_severities
+/ severity_variants and the `severities` parameter of RandomCorruptionGPU put them to use through
+ops.corrupt_batch_u8 (one launch for a batch with its own kind and strength per image). Opt-in: with the
+default (3,) every call and every random draw is the one without it.
 """
 import random
 
@@ -60,6 +64,84 @@ def env_extra_variants(value=None):
     if bad:
         raise ValueError(f"MX_EXTRA_VARIANTS names {', '.join(EXTRA_VARIANTS)} only; got {bad}")
     return [EXTRA_VARIANTS[k] for k in dict.fromkeys(names)]
+
+
+# Severity levels 1..5 of every corruption; constants of this project. Level 3 is the reference's
+# setting in every row (NOISE_SIGMA, BLUR_KERNEL, DOWNSCALE_FACTOR, JPEG_QUALITY); the JPEG row is
+# ImageNet-C's five qualities.
+SEVERITY_LEVELS = (1, 2, 3, 4, 5)
+DEFAULT_SEVERITIES = (3,)
+SEVERITY = {
+    "noise": (5, 10, 15, 25, 40),                    # sigma
+    "blur": (5, 7, 9, 13, 17),                       # kernel size k, at BLUR_ANGLE_DEG
+    "lowres": (0.75, 0.625, 0.5, 0.375, 0.25),       # down-scale factor
+    "jpeg": (25, 18, 15, 10, 7),                     # quality
+}
+KIND_VARIANTS = {"noise": ("Test_Noise", "Noise"), "blur": ("Test_Blur", "Blur"), "lowres": ("Test_LowRes", "LowRes"),
+                 "jpeg": EXTRA_VARIANTS["jpeg"]}  # kind -> (its level-3 test-set variant, short name)
+
+
+def check_severities(levels):
+    """levels as a tuple of ints; ValueError for an empty choice or a level outside 1..5."""
+    try:
+        out = tuple(int(v) for v in levels)
+        bad = [v for v, o in zip(levels, out) if o not in SEVERITY_LEVELS or float(v) != o]
+    except (TypeError, ValueError):
+        out, bad = (), [levels]
+    if bad or not out:
+        raise ValueError(f"severities must be a non-empty choice of the levels 1..5; got {levels!r}")
+    return out
+
+
+def env_severities(value=None):
+    """The severity levels of a run: `value`, or MX_SEVERITIES, a comma-separated list of levels 1..5
+    (default 3, the reference's setting: every call and every random draw as without the switch)."""
+    import os
+    value = os.environ.get("MX_SEVERITIES", "") if value is None else value
+    if isinstance(value, str):
+        value = [k.strip() for k in value.split(",") if k.strip()] or DEFAULT_SEVERITIES
+    elif isinstance(value, int):
+        value = [value]
+    return check_severities(value)
+
+
+def severity_value(kind, level):
+    """The strength of `kind` at `level`: sigma, kernel size, down-scale factor or JPEG quality."""
+    if kind not in SEVERITY or level not in SEVERITY_LEVELS:
+        raise ValueError(f"no severity {level!r} of corruption {kind!r}")
+    return SEVERITY[kind][level - 1]
+
+
+_TAPS = {}
+
+
+def _blur_taps(k, angle_deg=BLUR_ANGLE_DEG):
+    if (k, angle_deg) not in _TAPS:
+        _TAPS[(k, angle_deg)] = kernel_taps(motion_blur_kernel(k, angle_deg))
+    return _TAPS[(k, angle_deg)]
+
+
+def severity_spec(kind, level):
+    """The ops.corrupt_batch_u8 spec of `kind` at `level`."""
+    v = severity_value(kind, level)
+    if kind == "noise":
+        return ops.CorruptSpec(ops.CORRUPT_NOISE, float(v))
+    if kind == "blur":
+        return ops.CorruptSpec(ops.CORRUPT_BLUR, _blur_taps(v))
+    if kind == "lowres":
+        return ops.CorruptSpec(ops.CORRUPT_LOWRES, float(v))
+    return ops.CorruptSpec(ops.CORRUPT_JPEG, int(v))
+
+
+def severity_variants(severities=None, extra=None):
+    """The test sets MX_SEVERITIES adds, as [(variant, short name, kind, level)]: for every corrupted
+    variant that is built anyway (the reference's Noise / Blur / LowRes, then the MX_EXTRA_VARIANTS
+    ones) and every level other than 3, ascending, Test_<Kind>_s<L> / <Kind>-s<L>. Level 3 is the plain
+    Test_<Kind>, so there is no _s3 set. `severities` / `extra`: as env_severities / env_extra_variants."""
+    levels = sorted(set(env_severities(severities)) - {3})
+    built = [KIND_VARIANTS[k] for k in DEFAULT_KINDS] + env_extra_variants(extra)
+    kinds = {v: k for k, v in KIND_VARIANTS.items()}
+    return [(f"{var}_s{lv}", f"{short}-s{lv}", kinds[(var, short)], lv) for var, short in built for lv in levels]
 
 
 def _choice(kinds):
@@ -188,21 +270,48 @@ class RandomCorruption:
 class RandomCorruptionGPU:
     """Device form for uint8 HWC tensors: same decision rule (keep with prob 1-p, else a uniform choice
     of `kinds`: noise / blur / lowres by default) drawn from Python's `random` like the reference; noise
-    from Philox. The images are RGB here, so a "jpeg" draw compresses them as RGB."""
+    from Philox. The images are RGB here, so a "jpeg" draw compresses them as RGB.
+    severities: the levels a corrupted image draws from, random.choice(severities) after its kind. The
+    default (3,) draws nothing more and makes exactly the calls the class made before the parameter;
+    anything else goes through ops.corrupt_batch_u8, and batch(imgs) corrupts a list of frames of any
+    sizes in one call."""
 
     CODES = {"noise": ops.CORRUPT_NOISE, "blur": ops.CORRUPT_BLUR, "lowres": ops.CORRUPT_LOWRES,
              "jpeg": ops.CORRUPT_JPEG}
 
-    def __init__(self, p: float = 0.5, kinds=DEFAULT_KINDS):
+    def __init__(self, p: float = 0.5, kinds=DEFAULT_KINDS, severities=DEFAULT_SEVERITIES):
         self.p = p
         self.kinds = check_kinds(kinds)
+        self.severities = check_severities(severities)
 
     def __call__(self, img):
         if random.random() > self.p:
             return img
-        code = self.CODES[_choice(self.kinds)]
-        return ops.corrupt_u8(img[None], [code], sigma=NOISE_SIGMA, seed=random.getrandbits(63),
-                              factor=DOWNSCALE_FACTOR, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING)[0]
+        kind = _choice(self.kinds)
+        if self.severities == DEFAULT_SEVERITIES:
+            return ops.corrupt_u8(img[None], [self.CODES[kind]], sigma=NOISE_SIGMA, seed=random.getrandbits(63),
+                                  factor=DOWNSCALE_FACTOR, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING)[0]
+        spec = severity_spec(kind, random.choice(self.severities))
+        return ops.corrupt_batch_u8([img], [spec], seed=random.getrandbits(63), subsampling=JPEG_SUBSAMPLING)[0]
+
+    def batch(self, imgs):
+        """The decision rule per frame, in order (keep draw, then kind, then level), one seed draw for
+        the call, and one ops.corrupt_batch_u8 call for the frames that are corrupted; the others are
+        returned as they are."""
+        picks = {}
+        for i in range(len(imgs)):
+            if random.random() > self.p:
+                continue
+            kind = _choice(self.kinds)
+            picks[i] = severity_spec(kind, random.choice(self.severities))
+        seed = random.getrandbits(63)
+        out = list(imgs)
+        if picks:
+            got = ops.corrupt_batch_u8([imgs[i] for i in picks], list(picks.values()), seed=seed,
+                                       subsampling=JPEG_SUBSAMPLING)
+            for i, g in zip(picks, got):
+                out[i] = g
+        return out
 
 
 def patch_ultralytics_augmentations():

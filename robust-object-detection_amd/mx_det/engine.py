@@ -212,9 +212,10 @@ def evaluate(model, loader, ann_file, dev, per_class=False, device_eval=None):
 def train_frcnn(cfg):
     """cfg: dict with SEED, EPOCHS, BATCH_SIZE, LR, WEIGHT_DECAY, MOMENTUM, TRAIN_IMG, TRAIN_ANN, VAL_IMG,
     VAL_ANN, OUT_DIR, AUGMENT (bool), optional WEIGHTS (checkpoint path), NUM_WORKERS, CORRUPTIONS (the
-    kinds AUGMENT draws from: a list or comma-separated string, else MX_CORRUPTIONS, else noise,blur,lowres)."""
+    kinds AUGMENT draws from: a list or comma-separated string, else MX_CORRUPTIONS, else noise,blur,lowres),
+    SEVERITIES (the levels 1..5 it draws from, else MX_SEVERITIES, else 3)."""
     from .dataset import COCODetectionDataset, collate_fn, uint8_transform
-    from .augment import RandomCorruptionGPU, env_kinds
+    from .augment import DEFAULT_SEVERITIES, RandomCorruptionGPU, env_kinds, env_severities
 
     set_seed(cfg["SEED"])
     dev, world, rank = init_device()
@@ -268,7 +269,9 @@ def train_frcnn(cfg):
     it_global = 0
     # cfg CORRUPTIONS / MX_CORRUPTIONS: the kinds an augmented run draws from (default: the reference's)
     kinds = env_kinds(cfg.get("CORRUPTIONS"))
-    corrupt = RandomCorruptionGPU(p=0.5, kinds=kinds) if cfg.get("AUGMENT") else None
+    # cfg SEVERITIES / MX_SEVERITIES: the levels a corrupted frame draws from (default 3: as without it)
+    severities = env_severities(cfg.get("SEVERITIES"))
+    corrupt = RandomCorruptionGPU(p=0.5, kinds=kinds, severities=severities) if cfg.get("AUGMENT") else None
     history, best_ckpt, last_ckpt = out_dir / "history.jsonl", out_dir / "best.pth", out_dir / "last.pth"
     t0 = time.time()
     # cfg["TIMER"] = {"warmup": W}: bench.py --mode script's clock -- after W optimizer steps the device
@@ -300,8 +303,8 @@ def train_frcnn(cfg):
         epoch_loss = 0.0
         for i, (images, targets) in enumerate(train_loader):
             imgs, tgs = _to_device_batch(images, targets, dev)  # no-op copies for device images
-            if corrupt is not None:
-                imgs = [corrupt(im) for im in imgs]
+            if corrupt is not None:  # the batch in one launch only for a severity sweep
+                imgs = [corrupt(im) for im in imgs] if severities == DEFAULT_SEVERITIES else corrupt.batch(imgs)
             loss_dict = ddp(imgs, tgs)
             losses = sum(loss for loss in loss_dict.values())
             optimizer.zero_grad(set_to_none=True)

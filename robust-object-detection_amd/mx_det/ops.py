@@ -10,6 +10,7 @@ plus fused ops the build adds (match_assign, multiscale_roi_align, anchors_level
 corrupt_u8, normalize_pad). Errors follow torchvision's TORCH_CHECK style: RuntimeError on bad
 rank/shape/device; empty inputs give empty outputs.
 """
+import collections
 import ctypes
 import math
 import os
@@ -713,6 +714,103 @@ def filter2d_u8(images, taps):
     out = torch.empty_like(x)
     call("mx_filter2d_u8", _p(x), B, H, W, C, (ctypes.c_float * max(len(t), 1))(*t), len(t) // 3, _p(out), _stream())
     return out
+
+
+CorruptSpec = collections.namedtuple("CorruptSpec", ("op", "param"), defaults=(None,))
+CorruptSpec.__doc__ = """One image's corruption in corrupt_batch_u8: (CORRUPT_NONE,), (CORRUPT_NOISE, sigma),
+(CORRUPT_BLUR, taps as (dy, dx, coef) rows), (CORRUPT_LOWRES, factor), (CORRUPT_JPEG, quality)."""
+
+_SEED_STEP = 0x9E3779B97F4A7C15  # image b's Philox seed is seed + _SEED_STEP * b (mx_corrupt_u8's rule)
+
+
+def corrupt_batch_tile():
+    """(rows, columns) of the output tile one workgroup of mx_corrupt_batch_u8 owns."""
+    rc = (ctypes.c_int32 * 2)()
+    call("mx_corrupt_batch_tile", rc)
+    return int(rc[0]), int(rc[1])
+
+
+def corrupt_batch_u8(images, specs, seed=0, noise=None, out=None, subsampling=2, bgr=False):
+    """The corruptions with one (kind, strength) per image, the whole batch in one device launch
+    (mx_corrupt_batch_u8; chunks of 16 images): images is uint8 [B,H,W,3] or a list of uint8 [H,W,3]
+    tensors of any sizes, specs one CorruptSpec (or plain tuple) per image. Each image gets the bits
+    corrupt_u8 / filter2d_u8 / corrupt_jpeg_u8 give for it alone: noise from Philox with image b's seed
+    seed + 0x9E3779B97F4A7C15 * b (or from `noise`: f32 like images, or a list of per-image fields),
+    low-res at nh, nw = max(1, int(H * factor)), max(1, int(W * factor)). CORRUPT_JPEG images are
+    copied by the launch and then compressed by corrupt_jpeg_u8 (`subsampling`, `bgr`), one call per
+    image size. out: a tensor / list like images to write into; an entry that is its own image runs in
+    place (noise and identity only). Returns a tensor for a tensor, a list for a list."""
+    batched = torch.is_tensor(images)
+    if batched:
+        _dev(images)
+        _check(images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3, "images must be uint8 [B,H,W,3]")
+        x = images.contiguous()
+        xs = list(x.unbind(0))
+    else:
+        xs = [im.contiguous() for im in images]
+        for im in xs:
+            _dev(im)
+            _check(im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3, "images must be uint8 [H,W,3]")
+    B = len(xs)
+    specs = [CorruptSpec(*s) for s in specs]
+    _check(len(specs) == B, "corrupt_batch_u8: one spec per image")
+    if out is None:
+        if batched:
+            out = torch.empty_like(x)
+            outs = list(out.unbind(0))
+        else:
+            outs = [torch.empty_like(im) for im in xs]
+    else:
+        if batched:
+            _check(torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == x.device and out.shape == x.shape
+                   and out.is_contiguous(), "corrupt_batch_u8: out must be a contiguous uint8 tensor like images")
+            outs = list(out.unbind(0))
+        else:
+            outs = list(out)
+            _check(len(outs) == B and all(torch.is_tensor(o) and o.dtype == torch.uint8 and o.shape == im.shape
+                                          and o.device == im.device and o.is_contiguous() for o, im in zip(outs, xs)),
+                   "corrupt_batch_u8: out must list one contiguous uint8 tensor like each image")
+    if B == 0:
+        return out if batched else outs
+    if noise is not None:
+        if torch.is_tensor(noise):
+            noise = noise.float().contiguous()
+        else:
+            noise = torch.cat([n.float().reshape(-1) for n in noise])
+        _dev(noise)
+        _check(noise.numel() == sum(im.numel() for im in xs), "noise field must match images")
+    descs = (_lib.CorruptDesc * B)()
+    taps, tap_sets, jpeg = [], {}, {}
+    for b, (im, o, sp) in enumerate(zip(xs, outs, specs)):
+        d = descs[b]
+        H, W = int(im.shape[0]), int(im.shape[1])
+        d.src, d.dst, d.H, d.W = im.data_ptr(), o.data_ptr(), H, W
+        op = int(sp.op)
+        d.op = CORRUPT_NONE if op == CORRUPT_JPEG else op
+        if op == CORRUPT_NOISE:
+            d.sigma = float(sp.param)
+            d.seed = (int(seed) + _SEED_STEP * b) & (2 ** 64 - 1)
+        elif op == CORRUPT_BLUR:
+            key = tuple((int(dy), int(dx), float(c)) for dy, dx, c in sp.param)
+            if key not in tap_sets:
+                tap_sets[key] = len(taps) // 3
+                taps.extend(v for row in key for v in row)
+            d.tap_off, d.ntaps = tap_sets[key], len(key)
+        elif op == CORRUPT_LOWRES:
+            d.nh, d.nw = max(1, int(H * sp.param)), max(1, int(W * sp.param))
+        elif op == CORRUPT_JPEG:
+            _check(1 <= int(sp.param) <= 100, "corrupt_batch_u8: quality must be 1..100")
+            jpeg.setdefault((H, W), []).append(b)
+    call("mx_corrupt_batch_u8", descs, B, (ctypes.c_float * max(len(taps), 1))(*taps), len(taps) // 3, _p(noise),
+         _stream())
+    if jpeg and batched:  # one size: the rows with quality 0 keep what the launch wrote
+        corrupt_jpeg_u8(x, [int(sp.param) if int(sp.op) == CORRUPT_JPEG else 0 for sp in specs], subsampling, bgr, out=out)
+    elif jpeg:
+        for idx in jpeg.values():
+            got = corrupt_jpeg_u8(torch.stack([xs[b] for b in idx]), [int(specs[b].param) for b in idx], subsampling, bgr)
+            for j, b in enumerate(idx):
+                outs[b].copy_(got[j])
+    return out if batched else outs
 
 
 IMAGE_MEAN = (0.485, 0.456, 0.406)

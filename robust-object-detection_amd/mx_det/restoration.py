@@ -356,20 +356,30 @@ class DevicePatchLoader:
 class RestorationBatcher:
     """uint8 clean patches [B,S,S,3] (host) -> (corrupted, clean) f32 NCHW in [0, 1] on the device;
     each patch gets random.choice(noise, blur, lowres) as in _apply_random_corruption (:92-100), or a
-    uniform choice of `kinds` when those are given ("jpeg": compression at augment.JPEG_QUALITY)."""
+    uniform choice of `kinds` when those are given ("jpeg": compression at augment.JPEG_QUALITY).
+    severities other than the default (3,): each patch also draws random.choice(severities) after its
+    kind, and the batch is one ops.corrupt_batch_u8 call (augment.SEVERITY: blind-severity training)."""
 
-    def __init__(self, dev, kinds=augment.DEFAULT_KINDS):
+    def __init__(self, dev, kinds=augment.DEFAULT_KINDS, severities=augment.DEFAULT_SEVERITIES):
         self.dev = dev
         self.kinds = augment.check_kinds(kinds)
+        self.severities = augment.check_severities(severities)
 
     def __call__(self, clean_u8):
         x = clean_u8.to(self.dev, non_blocking=True)
-        if self.kinds == augment.DEFAULT_KINDS:
-            codes = [random.choice((NOISE, BLUR, LOWRES)) for _ in range(x.shape[0])]
+        if self.severities != augment.DEFAULT_SEVERITIES:
+            specs = []
+            for _ in range(x.shape[0]):
+                kind = augment._choice(self.kinds)
+                specs.append(augment.severity_spec(kind, random.choice(self.severities)))
+            cor = ops.corrupt_batch_u8(x, specs, seed=random.getrandbits(62), subsampling=augment.JPEG_SUBSAMPLING)
         else:
-            codes = [augment.RandomCorruptionGPU.CODES[random.choice(list(self.kinds))] for _ in range(x.shape[0])]
-        cor = ops.corrupt_u8(x, codes, seed=random.getrandbits(62), quality=augment.JPEG_QUALITY,
-                             subsampling=augment.JPEG_SUBSAMPLING)
+            if self.kinds == augment.DEFAULT_KINDS:
+                codes = [random.choice((NOISE, BLUR, LOWRES)) for _ in range(x.shape[0])]
+            else:
+                codes = [augment.RandomCorruptionGPU.CODES[random.choice(list(self.kinds))] for _ in range(x.shape[0])]
+            cor = ops.corrupt_u8(x, codes, seed=random.getrandbits(62), quality=augment.JPEG_QUALITY,
+                                 subsampling=augment.JPEG_SUBSAMPLING)
         to = lambda t: t.permute(0, 3, 1, 2).float().div_(255.0)  # noqa: E731
         return to(cor), to(x)
 

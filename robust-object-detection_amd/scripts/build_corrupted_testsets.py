@@ -17,6 +17,10 @@ encode them instead.
 MX_EXTRA_VARIANTS=jpeg appends Test_JPEG after the reference's four: every image compressed at
 augment.JPEG_QUALITY (4:2:0) and decoded again on the device (ops.corrupt_jpeg_u8), then written at
 quality 95 like the others. It draws nothing from np.random, so the noise fields are unchanged.
+MX_SEVERITIES (levels 1..5, default 3) appends, after all of those, Test_<Kind>_s<L> for every corrupted
+variant built and every level L other than 3 (augment.SEVERITY; level 3 is the plain Test_<Kind>), each
+image through ops.corrupt_batch_u8. Their noise fields continue the one np.random stream, so the sets
+above keep their bytes.
 """
 import os
 import shutil
@@ -42,8 +46,18 @@ NAMES = ["pedestrian", "car", "van", "truck", "bus", "motor"]
 
 
 def variants():
-    """The reference's four variants, then those MX_EXTRA_VARIANTS names."""
-    return VARIANTS + [v for v, _ in augment.env_extra_variants()]
+    """The reference's four variants, then those MX_EXTRA_VARIANTS names, then the MX_SEVERITIES sets."""
+    return VARIANTS + [v for v, _ in augment.env_extra_variants()] + [v[0] for v in augment.severity_variants()]
+
+
+def corrupt_severity(img_bgr, kind, level):
+    """`kind` at severity `level` on a BGR uint8 device tensor [H, W, 3] (ops.corrupt_batch_u8); noise
+    takes the next field of the np.random stream, like Test_Noise."""
+    noise = None
+    if kind == "noise":
+        noise = np.random.normal(0, augment.severity_value(kind, level), tuple(img_bgr.shape)).astype(np.float32)
+        noise = torch.from_numpy(noise).to(img_bgr.device)[None]
+    return ops.corrupt_batch_u8(img_bgr[None], [augment.severity_spec(kind, level)], noise=noise, bgr=True)[0]
 
 
 def set_seed(seed):
@@ -57,6 +71,13 @@ def ensure_dir(p):
 def corrupt(img_bgr, variant):
     """One variant of build_corrupted_testsets.py:140-150 on a BGR uint8 image, a device tensor
     [H, W, 3] (returned on the device) or a numpy array (returned as numpy)."""
+    sev = {v[0]: v[2:] for v in augment.severity_variants()}
+    if variant in sev:
+        if torch.is_tensor(img_bgr):
+            return corrupt_severity(img_bgr, *sev[variant])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        t = torch.from_numpy(np.ascontiguousarray(img_bgr, dtype=np.uint8)).to(dev)
+        return corrupt_severity(t, *sev[variant]).cpu().numpy()
     if not torch.is_tensor(img_bgr):
         if variant == "Test_Noise":
             return augment.apply_noise(img_bgr, NOISE_SIGMA)

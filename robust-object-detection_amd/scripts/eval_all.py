@@ -5,7 +5,8 @@ FRCNN branch of the reference's eval_all.py (:79-156, :198-213) on MI355X; the U
 YOLO branches are outside this build's scope and are reported as skipped.
 Outputs keep the reference schema: experiments/eval_results.json ({model: {variant: {mAP50_95, mAP50,
 per_class_ap50}}}) and experiments/eval_results.csv. torchrun shards the images per rank.
-MX_EXTRA_VARIANTS=jpeg adds the Test_JPEG set (column JPEG) after the reference's four.
+MX_EXTRA_VARIANTS=jpeg adds the Test_JPEG set (column JPEG) after the reference's four; MX_SEVERITIES
+(levels 1..5, default 3) adds the Test_<Kind>_s<L> sets after those (columns Noise-s1 and so on).
 """
 import csv
 import json
@@ -14,7 +15,7 @@ from pathlib import Path
 
 import torch
 
-from mx_det.augment import EXTRA_VARIANTS, env_extra_variants
+from mx_det.augment import EXTRA_VARIANTS, env_extra_variants, severity_variants
 from mx_det.engine import dist_info, eval_frcnn_variant, init_device, load_frcnn_checkpoint
 
 VARIANTS = ["Test_Clean", "Test_Noise", "Test_Blur", "Test_LowRes"]
@@ -31,12 +32,16 @@ OUT_DIR = Path("experiments")
 
 
 def all_variants():
-    """The reference's four variants, then those MX_EXTRA_VARIANTS names."""
-    return VARIANTS + [v for v, _ in env_extra_variants()]
+    """The reference's four variants, then those MX_EXTRA_VARIANTS names, then the MX_SEVERITIES sets."""
+    return VARIANTS + [v for v, _ in env_extra_variants()] + [v[0] for v in severity_variants()]
 
 
 def short(v):
-    return SHORT[v] if v in SHORT else dict(EXTRA_VARIANTS.values())[v]
+    if v in SHORT:
+        return SHORT[v]
+    base, _, level = v.rpartition("_s")  # Test_<Kind>_s<L> -> <Kind>-s<L>
+    names = dict(SHORT, **dict(EXTRA_VARIANTS.values()))
+    return f"{names[base]}-s{level}" if base in names and level.isdigit() else names[v]
 
 
 def variant_paths(root, v):

@@ -10,7 +10,8 @@ restored by the HIP U-Net on the GPU (reflect pad, /255, U-Net, *255, clip, trun
 straight to detection, no host round trip and no JPEG re-encode. That skips the reference's JPEG
 round trip, so its mAP is not the reference's number: it goes to
 experiments/eval_restored_results_fused.json instead.
-MX_EXTRA_VARIANTS=jpeg evaluates the restored Test_JPEG set too (eval_all.all_variants()).
+MX_EXTRA_VARIANTS=jpeg evaluates the restored Test_JPEG set too, MX_SEVERITIES the restored
+Test_<Kind>_s<L> sets (eval_all.all_variants()).
 """
 import os
 from pathlib import Path

@@ -6,7 +6,7 @@ do the JPEG decode (mx_det.jpeg.read_file; PIL for the files it does not handle)
 encode (mx_det.jpeg.write_file), both bit-identical to libjpeg-turbo: pixels never visit the host.
 MX_JPEG_ENCODE=host encodes with PIL instead; MX_JPEG_DECODE=device decodes the scan on the device
 too (the default decodes it on the host). The fused eval path (eval_restored.py) skips this step.
-MX_EXTRA_VARIANTS=jpeg restores Test_JPEG as well.
+MX_EXTRA_VARIANTS=jpeg restores Test_JPEG as well, MX_SEVERITIES the Test_<Kind>_s<L> sets.
 """
 import os
 import shutil
@@ -18,7 +18,7 @@ from PIL import Image
 
 from scripts import eval_restored
 from mx_det import jpeg
-from mx_det.augment import env_extra_variants
+from mx_det.augment import env_extra_variants, severity_variants
 from mx_det.engine import init_device
 
 COCO_TESTSET_ROOT = Path("data/testsets/coco6")
@@ -27,8 +27,9 @@ VARIANTS_TO_RESTORE = ["Test_Noise", "Test_Blur", "Test_LowRes"]
 
 
 def variants_to_restore():
-    """The reference's three corrupted variants, then those MX_EXTRA_VARIANTS names."""
-    return VARIANTS_TO_RESTORE + [v for v, _ in env_extra_variants()]
+    """The reference's three corrupted variants, then those MX_EXTRA_VARIANTS names, then the
+    MX_SEVERITIES sets."""
+    return VARIANTS_TO_RESTORE + [v for v, _ in env_extra_variants()] + [v[0] for v in severity_variants()]
 
 
 def read_rgb(path, dev):

@@ -13,7 +13,8 @@ frame in the training thread. MX_PATCH_LOADER=device decodes them on the device 
 (mx_det.restoration.DevicePatchLoader: only the crop is reconstructed; MX_JPEG_DECODE picks where the
 entropy decode runs); for a given seed its patch sequence differs from the host loader's.
 MX_CORRUPTIONS (comma-separated; default noise,blur,lowres, the reference's) names the corruptions the
-patches draw from; jpeg adds compression at augment.JPEG_QUALITY.
+patches draw from; jpeg adds compression at augment.JPEG_QUALITY. MX_SEVERITIES (levels 1..5, default
+3) names the severity levels each patch draws from (augment.SEVERITY; blind-severity training).
 """
 import json
 import os
@@ -23,7 +24,7 @@ from pathlib import Path
 import torch
 
 from mx_det import optim as mx_optim
-from mx_det.augment import env_kinds
+from mx_det.augment import env_kinds, env_severities
 from mx_det.engine import init_device, set_seed
 from mx_det.restoration import (CombinedLoss, DevicePatchLoader, RestorationBatcher, RestorationDataset, collate_u8,
                                 train_epoch, validate)
@@ -51,6 +52,7 @@ def main(train_dir=TRAIN_IMG_DIR, val_dir=VAL_IMG_DIR, out_dir=OUT_DIR, epochs=E
     if patch_loader not in ("host", "device"):
         raise ValueError("MX_PATCH_LOADER is 'host' or 'device'")
     kinds = env_kinds()  # MX_CORRUPTIONS: what the patches are corrupted with (default noise,blur,lowres)
+    severities = env_severities()  # MX_SEVERITIES: the levels they draw from (default 3)
     set_seed(SEED)
     dev, _, _ = init_device()
     out_dir = Path(out_dir)
@@ -76,7 +78,7 @@ def main(train_dir=TRAIN_IMG_DIR, val_dir=VAL_IMG_DIR, out_dir=OUT_DIR, epochs=E
     optimizer = AdamW(model.parameters(), lr=LR, weight_decay=1e-4)
     scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=epochs, eta_min=1e-6)
     criterion = CombinedLoss(ssim_weight=0.3)
-    batcher = RestorationBatcher(dev, kinds=kinds)
+    batcher = RestorationBatcher(dev, kinds=kinds, severities=severities)
     history, best_ckpt, last_ckpt = out_dir / "history.jsonl", out_dir / "best.pth", out_dir / "last.pth"
     best_psnr, t0 = 0.0, time.time()
     for epoch in range(1, epochs + 1):
