@@ -136,7 +136,7 @@ __device__ __forceinline__ void split8(const float4 a, const float4 b, uint4& hi
 // torch.optim.SGD's update of one element (scripts/train_frcnn_baseline.py:149-153):
 //   d = g + wd * p;  buf = first ? d : momentum * buf + (1 - dampening) * d;
 //   d = nesterov ? d + momentum * buf : buf;  p -= lr * d
-// Shared by sgd_kernel (mx_optim.hip) and the pack-fused sgd_pack_kernel (mx_conv.hip), both built with
+// Shared by sgd_kernel (mx_optim.hip) and the pack-fused sgd_pack_kernel (mx_pack.hip), both built with
 // the same flags, so the two paths produce the same bits.
 __device__ __forceinline__ float sgd_update(float& p, float g, float& b, bool first, float lr, float momentum,
                                             float dampening, float wd, int nesterov) {
@@ -157,7 +157,7 @@ __device__ __forceinline__ float sgd_update(float& p, float g, float& b, bool fi
 // w1 = 1 - beta1, b2 = beta2, w2 = 1 - beta2, bc2_sqrt = sqrt(1 - beta2^step), step_size =
 // lr / (1 - beta1^step)) and rounded to f32 once. Every f32 op
 // rounds once: no contraction in here, whatever the flags of the file that inlines it, so
-// adamw_kernel (mx_optim.hip) and the pack-fused adamw_pack_kernel (mx_conv.hip) produce the same
+// adamw_kernel (mx_optim.hip) and the pack-fused adamw_pack_kernel (mx_pack.hip) produce the same
 // bits. Division and square root are the IEEE-rounded ones.
 struct AdamwHyper {
   float decay, w1, b2, w2, eps;
@@ -185,6 +185,109 @@ inline AdamwHyper adamw_hyper(double lr, double beta1, double beta2, double eps,
 inline void adamw_bias(double lr, double beta1, double beta2, int64_t step, float& step_size, float& bc2_sqrt) {
   step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
   bc2_sqrt = (float)pow(1.0 - pow(beta2, (double)step), 0.5);
+}
+
+// An update rule names what one optimizer's kernels differ in: NS state arrays, the constants of a
+// launch (Hyper) and of a tensor (Tensor), and apply() = the element update above. The multi-tensor
+// kernels (mx_optim.hip) and the pack-fused ones (mx_pack.hip) are written once over a rule R; the
+// state is indexed by unrolled constants only, so it lives in registers.
+struct SgdHyper {
+  float lr, momentum, dampening, wd;
+  int nesterov;
+};
+struct SgdRule {
+  static constexpr int NS = 1;  // buf
+  typedef SgdHyper Hyper;
+  struct Tensor {
+    int first;  // the tensor takes its first momentum step
+  };
+  static __device__ __forceinline__ void apply(float& p, float g, float (&s)[NS], const Hyper& h, const Tensor& t) {
+    sgd_update(p, g, s[0], t.first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
+  }
+};
+struct AdamwRule {
+  static constexpr int NS = 2;  // exp_avg, exp_avg_sq
+  typedef AdamwHyper Hyper;
+  struct Tensor {
+    float step_size, bc2_sqrt;
+  };
+  static __device__ __forceinline__ void apply(float& p, float g, float (&s)[NS], const Hyper& h, const Tensor& t) {
+    adamw_update(p, g, s[0], s[1], h, t.step_size, t.bc2_sqrt);
+  }
+};
+
+// p, g and every state array 16-B aligned: the float4 forms below may be used
+template <typename R>
+__device__ __forceinline__ bool update_aligned(const float* p, const float* g, float* const (&s)[R::NS]) {
+  uintptr_t bits = (uintptr_t)p | (uintptr_t)g;
+#pragma unroll
+  for (int k = 0; k < R::NS; ++k) bits |= (uintptr_t)s[k];
+  return (bits & 15u) == 0;
+}
+// element i (update1) / elements i .. i + 3 as float4s (update4) of p and the state arrays updated in
+// place with gradient g; the new parameter value(s) are handed back
+template <typename R>
+__device__ __forceinline__ float update1(float* p, const float* g, float* const (&s)[R::NS], int64_t i,
+                                         const typename R::Hyper& h, const typename R::Tensor& t) {
+  float pv = p[i], sv[R::NS];
+#pragma unroll
+  for (int k = 0; k < R::NS; ++k) sv[k] = s[k][i];
+  R::apply(pv, g[i], sv, h, t);
+  p[i] = pv;
+#pragma unroll
+  for (int k = 0; k < R::NS; ++k) s[k][i] = sv[k];
+  return pv;
+}
+template <typename R>
+__device__ __forceinline__ void update4(float* p, const float* g, float* const (&s)[R::NS], int64_t i,
+                                        const typename R::Hyper& h, const typename R::Tensor& t, float (&pv)[4]) {
+  float gv[4], sv[R::NS][4];
+  *(float4*)pv = *(const float4*)(p + i);
+#pragma unroll
+  for (int k = 0; k < R::NS; ++k) *(float4*)sv[k] = *(const float4*)(s[k] + i);
+  *(float4*)gv = *(const float4*)(g + i);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float sq[R::NS];
+#pragma unroll
+    for (int k = 0; k < R::NS; ++k) sq[k] = sv[k][q];
+    R::apply(pv[q], gv[q], sq, h, t);
+#pragma unroll
+    for (int k = 0; k < R::NS; ++k) sv[k][q] = sq[k];
+  }
+  *(float4*)(p + i) = *(const float4*)pv;
+#pragma unroll
+  for (int k = 0; k < R::NS; ++k) *(float4*)(s[k] + i) = *(const float4*)sv[k];
+}
+
+// The streaming body of every multi-tensor update: block blk of a 256-thread launch takes elements
+// [blk * UPDATE_PER_BLOCK, +UPDATE_PER_BLOCK) of an n-element tensor, as float4s when every pointer
+// is 16-B aligned (then a scalar tail), else element by element.
+static constexpr int UPDATE_PER_BLOCK = 2048;
+template <typename R>
+__device__ __forceinline__ void update_chunk(float* p, const float* __restrict__ g, float* const (&s)[R::NS], int64_t n,
+                                             int64_t blk, const typename R::Hyper& h, const typename R::Tensor& t) {
+  const int64_t e0 = blk * UPDATE_PER_BLOCK, e1 = min<int64_t>(n, e0 + UPDATE_PER_BLOCK);
+  if (update_aligned<R>(p, g, s)) {
+    float pv[4];
+    for (int64_t e = e0 + threadIdx.x * 4; e + 3 < e1; e += 256 * 4) update4<R>(p, g, s, e, h, t, pv);
+    const int64_t tail = e0 + ((e1 - e0) & ~(int64_t)3);
+    for (int64_t e = tail + threadIdx.x; e < e1; e += 256) update1<R>(p, g, s, e, h, t);
+  } else {
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) update1<R>(p, g, s, e, h, t);
+  }
+}
+
+// Block -> job through prefix sums: the last j < n with prefix[j] <= b (prefix[0] == 0)
+template <typename T>
+__device__ __forceinline__ int last_job(const T* prefix, int n, int64_t b) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (prefix[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
 }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

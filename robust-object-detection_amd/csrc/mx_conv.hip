@@ -18,6 +18,7 @@
 // tiles are staged pixel-major (coalesced) and read transposed with ds_read_b64_tr_b16, split-K
 // over pixels with f32 atomic accumulation.
 #include "mx_common.h"
+#include "mx_conv_layout.h"
 #include "mx_dma.h"
 
 #include <vector>
@@ -2358,513 +2359,6 @@ __global__ void transpose_w_kernel(const uint16_t* __restrict__ w, int64_t K, in
   wt[(c * RS + rs) * K + k] = w[i];
 }
 
-// Per-step weight preparation, one pass over the f32 master weight w[K][C][R][S] (torch layout):
-//   wk [K][R][S][Cpad] bf16      — fwd / wgrad operand (input channels zero-padded to Cpad)
-//   wt [class][Cpad][Rc][Sc][Kpad] bf16 — dgrad operand, taps grouped by stride-parity class
-// Tiles go through LDS so the f32 reads and both bf16 writes run along their contiguous axes
-// (pack_plan; R*S <= 196).
-struct PackP {
-  const float* w;
-  uint16_t* wk;
-  uint16_t* wt;
-  int64_t K, C, Cpad, Kpad;
-  int R, S, st_h, st_w;
-  int64_t off[4];
-  int Rc[4], Sc[4];
-  int dense;  // wt as [R][S][Cpad][Kpad]: the 1x1-GEMM dgrad operand of a conv whose output is 1x1
-  // split: bf16x3 operands -- every layout is written twice, plane 0 = bf16(w) (hi) and plane 1 =
-  // bf16(w - hi) (lo), the lo plane wk_plane / wt_plane elements after the hi plane
-  int split;
-  int64_t wk_plane, wt_plane;
-  // tiling (pack_plan): wk tiles = kr output rows x cw input channels x all taps (nwk of them, first),
-  // then wt tiles = 64 output channels x tct input channels x all taps
-  int kr, cw, tct;
-  int64_t nwk, nwt;
-};
-
-// Two tile kinds, each with contiguous f32 reads and 128-B bf16 write runs (values staged in LDS as
-// bf16, so the rounding is the one f2bf of the f32 master value):
-//  * wk tile: kr whole output rows (cw input channels x all taps each; cw = Cpad unless one row
-//    exceeds the LDS tile) -- a per-row [C][RS] -> [RS][Cpad] transpose, both sides contiguous;
-//  * wt tile: 64 output channels x tct input channels x all taps -- read as 64 contiguous runs of
-//    tct*RS floats, written along the innermost Kpad axis as output-channel pairs.
-static constexpr int PACK_LDS = 25600;  // bf16 elements (50 KiB)
-static constexpr int PK = 64;
-
-__device__ __forceinline__ uint32_t fdiv(uint32_t a, uint32_t d, float inv) {  // a / d for a < 2^22
-  uint32_t q = (uint32_t)((float)a * inv);
-  if (q * d > a) --q;
-  else if ((q + 1) * d <= a) ++q;
-  return q;
-}
-
-__device__ __forceinline__ void st_bf2(uint16_t* d, uint16_t a, uint16_t b, bool two) {
-  if (two && ((uintptr_t)d & 3) == 0) {
-    *(uint32_t*)d = (uint32_t)a | ((uint32_t)b << 16);
-  } else {
-    d[0] = a;
-    if (two) d[1] = b;
-  }
-}
-
-// plane 0 (hi) / 1 (lo) of the bf16x3 split of an f32 weight
-__device__ __forceinline__ uint16_t plane_bf(float v, int plane) {
-  const uint16_t h = f2bf(v);
-  return plane ? f2bf(v - bf2f(h)) : h;
-}
-
-// T[row * ldt + j] = bf16(w[(k0 + row) * C * RS + c0 * RS + j]) for j < n_valid (zero past the real
-// input channels / output rows); ldt % 4 == 0. plane 1: the lo part bf16(w - bf16(w)).
-__device__ __forceinline__ void pack_stage(const PackP& p, int64_t k0, int64_t c0, int rows, int width, int ldt,
-                                           uint16_t* T, int plane) {
-  const int RS = p.R * p.S;
-  const int64_t cend = p.C < c0 + width / RS ? p.C : c0 + width / RS;
-  const int nvalid = cend > c0 ? (int)((cend - c0) * RS) : 0;
-  // U independent loads in flight per thread before the first LDS write (a load -> ds_write loop
-  // would wait out the full memory latency once per element)
-  constexpr int U = 8;
-  if ((p.C & 3) == 0 && (c0 & 3) == 0 && (width & 3) == 0 && ((uintptr_t)p.w & 15) == 0) {
-    // float4 path: every row run starts 16-B aligned and holds whole groups of 4
-    const int w4 = width >> 2, total4 = rows * w4, nv4 = nvalid >> 2;
-    const float inv4 = 1.f / (float)w4;
-    for (int base = 0; base < total4; base += 256 * U) {
-      float4 v[U];
-      int dst[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int e = base + u * 256 + threadIdx.x;
-        const int row = (int)fdiv((uint32_t)e, (uint32_t)w4, inv4), j4 = e - row * w4;
-        const int64_t k = k0 + row;
-        dst[u] = e < total4 ? row * ldt + 4 * j4 : -1;
-        v[u] = (e < total4 && k < p.K && j4 < nv4) ? *(const float4*)(p.w + (k * p.C + c0) * RS + 4 * j4)
-                                                   : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (dst[u] >= 0)
-          *(uint2*)(T + dst[u]) =
-              make_uint2((uint32_t)plane_bf(v[u].x, plane) | ((uint32_t)plane_bf(v[u].y, plane) << 16),
-                         (uint32_t)plane_bf(v[u].z, plane) | ((uint32_t)plane_bf(v[u].w, plane) << 16));
-    }
-    __syncthreads();
-    return;
-  }
-  const float inv = 1.f / (float)width;
-  const int total = rows * width;
-  for (int base = 0; base < total; base += 256 * U) {
-    float v[U];
-    int dst[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int e = base + u * 256 + threadIdx.x;
-      const int row = (int)fdiv((uint32_t)e, (uint32_t)width, inv), j = e - row * width;
-      const int64_t k = k0 + row;
-      dst[u] = e < total ? row * ldt + j : -1;
-      v[u] = (e < total && k < p.K && j < nvalid) ? p.w[(k * p.C + c0) * RS + j] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (dst[u] >= 0) T[dst[u]] = plane_bf(v[u], plane);
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ void pack_wk_tile(const PackP& p, int64_t t, uint16_t* T, int plane) {
-  const int RS = p.R * p.S;
-  const int64_t nc = (p.Cpad + p.cw - 1) / p.cw;
-  const int64_t k0 = (t / nc) * p.kr, c0 = (t % nc) * p.cw;
-  const int cwv = (int)(p.Cpad - c0 < p.cw ? p.Cpad - c0 : p.cw);
-  const int width = cwv * RS, ldt = width + 4;
-  pack_stage(p, k0, c0, p.kr, width, ldt, T, plane);
-  uint16_t* wk = p.wk + plane * p.wk_plane;
-  const int h = (cwv + 1) >> 1, per = RS * h;  // channel pairs per (row, tap)
-  const float inv_per = 1.f / (float)per, inv_h = 1.f / (float)h;
-  for (int e = threadIdx.x; e < p.kr * per; e += 256) {
-    const int row = (int)fdiv((uint32_t)e, (uint32_t)per, inv_per), rem = e - row * per;
-    const int rs = (int)fdiv((uint32_t)rem, (uint32_t)h, inv_h), c2 = rem - rs * h;
-    const int64_t k = k0 + row;
-    if (k >= p.K) continue;
-    const int cc = 2 * c2;
-    const uint16_t* tt = T + row * ldt + cc * RS + rs;
-    st_bf2(wk + (k * RS + rs) * p.Cpad + c0 + cc, tt[0], cc + 1 < cwv ? tt[RS] : (uint16_t)0, cc + 1 < cwv);
-  }
-}
-
-__device__ __forceinline__ void pack_wt_tile(const PackP& p, int64_t t, uint16_t* T, int plane) {
-  const int RS = p.R * p.S;
-  const int64_t nc = (p.Cpad + p.tct - 1) / p.tct;
-  const int64_t k0 = (t / nc) * PK, c0 = (t % nc) * p.tct;
-  const int width = p.tct * RS, ldt = width + 4;
-  pack_stage(p, k0, c0, PK, width, ldt, T, plane);
-  uint16_t* wt = p.wt + plane * p.wt_plane;
-  constexpr int PK2 = PK / 2;
-  const int per = RS * PK2;
-  const float inv_per = 1.f / (float)per;
-  for (int e = threadIdx.x; e < p.tct * per; e += 256) {
-    const int cc = (int)fdiv((uint32_t)e, (uint32_t)per, inv_per), rem = e - cc * per;
-    const int rs = rem / PK2, k2 = rem % PK2;  // PK2 is a power of two
-    const int64_t k = k0 + 2 * k2, c = c0 + cc;
-    if (k >= p.Kpad || c >= p.Cpad) continue;
-    const uint16_t* tt = T + 2 * k2 * ldt + cc * RS + rs;
-    int64_t dst;
-    if (p.dense) {  // [R][S][Cpad][Kpad]: the 1x1-GEMM dgrad operand of a conv whose output is 1x1
-      dst = ((int64_t)rs * p.Cpad + c) * p.Kpad + k;
-    } else {  // tap-parity class q (r % st_h, s % st_w): [c][r / st_h][s / st_w][Kpad]
-      const int r = rs / p.S, sx = rs - r * p.S;
-      const int q = (r % p.st_h) * p.st_w + (sx % p.st_w);
-      dst = p.off[q] + ((c * p.Rc[q] + r / p.st_h) * p.Sc[q] + sx / p.st_w) * p.Kpad + k;
-    }
-    st_bf2(wt + dst, tt[0], tt[ldt], k + 1 < p.Kpad);
-  }
-}
-
-// tiles: nwk wk tiles, then nwt wt tiles; a split job's block writes both planes of its tile, the
-// second staging re-reading the f32 region it has just read (L2-hot) instead of another block
-// fetching it from HBM again
-__device__ __forceinline__ void pack_tile(const PackP& p, int64_t t) {
-  __shared__ uint16_t T[PACK_LDS];
-  const int np = p.split ? 2 : 1;
-  for (int plane = 0; plane < np; ++plane) {
-    if (plane) __syncthreads();  // the previous plane's writes have read T
-    if (t < p.nwk) pack_wk_tile(p, t, T, plane);
-    else pack_wt_tile(p, t - p.nwk, T, plane);
-  }
-}
-
-__global__ void __launch_bounds__(256) pack_weight_kernel(PackP p) { pack_tile(p, blockIdx.x); }
-
-// Every conv weight of a step in one launch: block -> (job, tile) through the tile prefix sums.
-__global__ void __launch_bounds__(256) pack_batched_kernel(const PackP* __restrict__ jobs, const int64_t* __restrict__ prefix,
-                                                           int njobs) {
-  const int64_t b = blockIdx.x;
-  int lo = 0, hi = njobs - 1;  // last job with prefix[j] <= b
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (prefix[mid] <= b) lo = mid; else hi = mid - 1;
-  }
-  const PackP p = jobs[lo];
-  pack_tile(p, b - prefix[lo]);
-}
-
-// ---------------------------------------------------------------------------------------------
-// SGD step fused with the operand pack: a conv weight's update and its bf16 operand layouts in ONE
-// pass (mx_sgd_pack_step). The per-step order was sgd_kernel (p, g, buf -> p, buf) and then
-// pack_batched_kernel re-reading every updated f32 weight twice (wk tile, wt tile); here a block owns
-// a kr x tc x (all taps) tile of w[K][C][R][S]: it updates the tile in registers (p, buf written back),
-// keeps the (hi, lo) bf16 pair of each new weight in LDS as one u32, and writes both the wk and the wt
-// layout from there. Each weight element is read once and written once per layout, as sgd + pack
-// would produce it (same sgd_update, same rounding). Non-conv parameters take the plain
-// multi-tensor SGD blocks of the same launch.
-struct SgdJob {
-  float* p;
-  float* b;
-  int64_t n;
-  int first, fused;
-  int kr, tc;    // fused tile: kr output rows x tc input channels x all taps (powers of two)
-  int64_t ncb;   // channel blocks (cdiv(Cpad, tc)) per row block
-  PackP pk;      // fused: pk.w == p
-};
-struct SgdHyper {
-  float lr, momentum, dampening, wd;
-  int nesterov;
-};
-static constexpr int SGDP_PER_BLOCK = 2048;
-
-__device__ __forceinline__ uint32_t hilo_word(float v) {  // bf16(v) | bf16(v - bf16(v)) << 16
-  const uint16_t h = f2bf(v);
-  return (uint32_t)h | ((uint32_t)f2bf(v - bf2f(h)) << 16);
-}
-
-__device__ __forceinline__ void sgd_plain_block(const SgdJob& J, const float* __restrict__ g, int64_t blk,
-                                                const SgdHyper& h) {
-  const int64_t e0 = blk * SGDP_PER_BLOCK, e1 = min<int64_t>(J.n, e0 + SGDP_PER_BLOCK);
-  float* __restrict__ p = J.p;
-  float* __restrict__ b = J.b;
-  const bool first = J.first;
-  if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)b)) & 15u) == 0) {
-    for (int64_t e = e0 + threadIdx.x * 4; e + 3 < e1; e += 256 * 4) {
-      float4 pv = *(float4*)(p + e), bv = *(float4*)(b + e);
-      const float4 gv = *(const float4*)(g + e);
-      sgd_update(pv.x, gv.x, bv.x, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-      sgd_update(pv.y, gv.y, bv.y, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-      sgd_update(pv.z, gv.z, bv.z, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-      sgd_update(pv.w, gv.w, bv.w, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-      *(float4*)(p + e) = pv;
-      *(float4*)(b + e) = bv;
-    }
-    const int64_t tail = e0 + ((e1 - e0) & ~(int64_t)3);
-    for (int64_t e = tail + threadIdx.x; e < e1; e += 256)
-      sgd_update(p[e], g[e], b[e], first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-  } else {
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256)
-      sgd_update(p[e], g[e], b[e], first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-  }
-}
-
-// The wk and wt layouts of one kr x tc x (all taps) tile whose new weights sit in LDS as (hi, lo) bf16
-// pairs (hilo_word), T[row * ldt + channel * RS + tap]; rows / channels past K / C hold 0.
-__device__ __forceinline__ void tile_store_layouts(const PackP& pk, int kr, int tc, int64_t k0, int64_t c0,
-                                                   const uint32_t* T, int ldt) {
-  const int RS = pk.R * pk.S;
-  const int np = pk.split ? 2 : 1;
-  // 2. wk [K][R][S][Cpad]: runs of tc channels per (row, tap), written as channel pairs
-  if (pk.wk) {
-    const int h2 = tc >> 1, per = RS * h2;
-    const float inv_per = 1.f / (float)per, inv_h = 1.f / (float)h2;
-    for (int e = threadIdx.x; e < kr * per; e += 256) {
-      const int row = (int)fdiv((uint32_t)e, (uint32_t)per, inv_per), rem = e - row * per;
-      const int rs = (int)fdiv((uint32_t)rem, (uint32_t)h2, inv_h), c2 = rem - rs * h2;
-      const int64_t k = k0 + row, c = c0 + 2 * c2;
-      if (k >= pk.K || c >= pk.Cpad) continue;
-      const uint32_t* tt = T + row * ldt + 2 * c2 * RS + rs;
-      const uint32_t a = tt[0], a2 = tt[RS];  // Cpad is even: c + 1 < Cpad
-      const int64_t dst = (k * RS + rs) * pk.Cpad + c;
-      for (int pl = 0; pl < np; ++pl)
-        *(uint32_t*)(pk.wk + pl * pk.wk_plane + dst) =
-            pl ? (a >> 16) | (a2 & 0xffff0000u) : (a & 0xffffu) | (a2 << 16);
-    }
-  }
-  // 3. wt (dgrad layout): runs along the output channels, written as output-channel pairs
-  if (pk.wt) {
-    const int kr2 = kr >> 1, per = RS * kr2;
-    const float inv_per = 1.f / (float)per, inv_k = 1.f / (float)kr2;
-    for (int e = threadIdx.x; e < tc * per; e += 256) {
-      const int cc = (int)fdiv((uint32_t)e, (uint32_t)per, inv_per), rem = e - cc * per;
-      const int rs = (int)fdiv((uint32_t)rem, (uint32_t)kr2, inv_k), k2 = rem - rs * kr2;
-      const int64_t k = k0 + 2 * k2, c = c0 + cc;
-      if (k >= pk.Kpad || c >= pk.Cpad) continue;
-      const uint32_t* tt = T + 2 * k2 * ldt + cc * RS + rs;
-      const uint32_t a = tt[0], a2 = tt[ldt];  // Kpad is even: k + 1 < Kpad
-      int64_t dst;
-      if (pk.dense) {
-        dst = ((int64_t)rs * pk.Cpad + c) * pk.Kpad + k;
-      } else {
-        const int r = rs / pk.S, sx = rs - r * pk.S;
-        const int q = (r % pk.st_h) * pk.st_w + (sx % pk.st_w);
-        dst = pk.off[q] + ((c * pk.Rc[q] + r / pk.st_h) * pk.Sc[q] + sx / pk.st_w) * pk.Kpad + k;
-      }
-      for (int pl = 0; pl < np; ++pl)
-        *(uint32_t*)(pk.wt + pl * pk.wt_plane + dst) =
-            pl ? (a >> 16) | (a2 & 0xffff0000u) : (a & 0xffffu) | (a2 << 16);
-    }
-  }
-}
-
-__device__ __forceinline__ void sgd_pack_tile(const SgdJob& J, const float* __restrict__ g, int64_t t,
-                                              const SgdHyper& h, uint32_t* T) {
-  const PackP& pk = J.pk;
-  const int RS = pk.R * pk.S;
-  const int kr = J.kr, tc = J.tc;
-  const int64_t k0 = (t / J.ncb) * kr, c0 = (t % J.ncb) * tc;
-  const int width = tc * RS, ldt = width + 1;  // odd row stride: column reads spread over the banks
-  const int64_t cend = pk.C < c0 + tc ? pk.C : c0 + tc;
-  const int nvalid = cend > c0 ? (int)((cend - c0) * RS) : 0;
-  const bool first = J.first;
-  float* __restrict__ p = J.p;
-  float* __restrict__ b = J.b;
-  // 1. update the tile: row k's run of nvalid weights starts at (k * C + c0) * RS
-  if ((pk.C & 3) == 0 && ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)b)) & 15u) == 0) {
-    const int w4 = width >> 2, nv4 = nvalid >> 2;
-    const float inv4 = 1.f / (float)w4;
-    for (int e = threadIdx.x; e < kr * w4; e += 256) {
-      const int row = (int)fdiv((uint32_t)e, (uint32_t)w4, inv4), j4 = e - row * w4;
-      const int64_t k = k0 + row;
-      uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
-      if (k < pk.K && j4 < nv4) {
-        const int64_t i = (k * pk.C + c0) * RS + 4 * j4;
-        float4 pv = *(float4*)(p + i), bv = *(float4*)(b + i);
-        const float4 gv = *(const float4*)(g + i);
-        sgd_update(pv.x, gv.x, bv.x, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-        sgd_update(pv.y, gv.y, bv.y, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-        sgd_update(pv.z, gv.z, bv.z, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-        sgd_update(pv.w, gv.w, bv.w, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-        *(float4*)(p + i) = pv;
-        *(float4*)(b + i) = bv;
-        o0 = hilo_word(pv.x); o1 = hilo_word(pv.y); o2 = hilo_word(pv.z); o3 = hilo_word(pv.w);
-      }
-      uint32_t* d = T + row * ldt + 4 * j4;
-      d[0] = o0; d[1] = o1; d[2] = o2; d[3] = o3;
-    }
-  } else {
-    const float inv = 1.f / (float)width;
-    for (int e = threadIdx.x; e < kr * width; e += 256) {
-      const int row = (int)fdiv((uint32_t)e, (uint32_t)width, inv), j = e - row * width;
-      const int64_t k = k0 + row;
-      uint32_t o = 0;
-      if (k < pk.K && j < nvalid) {
-        const int64_t i = (k * pk.C + c0) * RS + j;
-        float pv = p[i], bv = b[i];
-        sgd_update(pv, g[i], bv, first, h.lr, h.momentum, h.dampening, h.wd, h.nesterov);
-        p[i] = pv;
-        b[i] = bv;
-        o = hilo_word(pv);
-      }
-      T[row * ldt + j] = o;
-    }
-  }
-  __syncthreads();
-  tile_store_layouts(pk, kr, tc, k0, c0, T, ldt);
-}
-
-// block -> (job, tile or 2048-element chunk) through the prefix sums; grads by job index (their
-// pointers change more often than the job table)
-__global__ void __launch_bounds__(256) sgd_pack_kernel(const SgdJob* __restrict__ jobs, const int64_t* __restrict__ prefix,
-                                                       const float* const* __restrict__ grads, int njobs, SgdHyper h) {
-  extern __shared__ uint32_t Tsm[];
-  const int64_t bidx = blockIdx.x;
-  int lo = 0, hi = njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (prefix[mid] <= bidx) lo = mid; else hi = mid - 1;
-  }
-  const SgdJob J = jobs[lo];
-  if (J.fused) sgd_pack_tile(J, grads[lo], bidx - prefix[lo], h, Tsm);
-  else sgd_plain_block(J, grads[lo], bidx - prefix[lo], h);
-}
-
-// ---------------------------------------------------------------------------------------------
-// AdamW step fused with the operand pack (mx_adamw_pack_step): the same tiling as the SGD form above
-// with adamw_update (mx_common.h) as the update -- a block owns a kr x tc x (all taps) tile, updates
-// it in registers (p, exp_avg, exp_avg_sq written back), and writes wk and wt from the (hi, lo) words
-// in LDS. One launch serves a parameter group that shares one step number, so the bias corrections
-// are launch arguments beside the other constants.
-struct AdamwJob {
-  float* p;
-  float* m;
-  float* v;
-  int64_t n;
-  int fused;
-  int kr, tc;
-  int64_t ncb;
-  PackP pk;  // fused: pk.w == p
-};
-struct AdamwStep {
-  AdamwHyper h;
-  float step_size, bc2_sqrt;
-};
-
-__device__ __forceinline__ void adamw_plain_block(const AdamwJob& J, const float* __restrict__ g, int64_t blk,
-                                                  const AdamwStep& s) {
-  const int64_t e0 = blk * SGDP_PER_BLOCK, e1 = min<int64_t>(J.n, e0 + SGDP_PER_BLOCK);
-  float* __restrict__ p = J.p;
-  float* __restrict__ m = J.m;
-  float* __restrict__ v = J.v;
-  if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15u) == 0) {
-    for (int64_t e = e0 + threadIdx.x * 4; e + 3 < e1; e += 256 * 4) {
-      float4 pv = *(float4*)(p + e), mv = *(float4*)(m + e), vv = *(float4*)(v + e);
-      const float4 gv = *(const float4*)(g + e);
-      adamw_update(pv.x, gv.x, mv.x, vv.x, s.h, s.step_size, s.bc2_sqrt);
-      adamw_update(pv.y, gv.y, mv.y, vv.y, s.h, s.step_size, s.bc2_sqrt);
-      adamw_update(pv.z, gv.z, mv.z, vv.z, s.h, s.step_size, s.bc2_sqrt);
-      adamw_update(pv.w, gv.w, mv.w, vv.w, s.h, s.step_size, s.bc2_sqrt);
-      *(float4*)(p + e) = pv;
-      *(float4*)(m + e) = mv;
-      *(float4*)(v + e) = vv;
-    }
-    const int64_t tail = e0 + ((e1 - e0) & ~(int64_t)3);
-    for (int64_t e = tail + threadIdx.x; e < e1; e += 256)
-      adamw_update(p[e], g[e], m[e], v[e], s.h, s.step_size, s.bc2_sqrt);
-  } else {
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256)
-      adamw_update(p[e], g[e], m[e], v[e], s.h, s.step_size, s.bc2_sqrt);
-  }
-}
-
-__device__ __forceinline__ void adamw_pack_tile(const AdamwJob& J, const float* __restrict__ g, int64_t t,
-                                                const AdamwStep& s, uint32_t* T) {
-  const PackP& pk = J.pk;
-  const int RS = pk.R * pk.S;
-  const int kr = J.kr, tc = J.tc;
-  const int64_t k0 = (t / J.ncb) * kr, c0 = (t % J.ncb) * tc;
-  const int width = tc * RS, ldt = width + 1;  // odd row stride: column reads spread over the banks
-  const int64_t cend = pk.C < c0 + tc ? pk.C : c0 + tc;
-  const int nvalid = cend > c0 ? (int)((cend - c0) * RS) : 0;
-  float* __restrict__ p = J.p;
-  float* __restrict__ m = J.m;
-  float* __restrict__ v = J.v;
-  // 1. update the tile: row k's run of nvalid weights starts at (k * C + c0) * RS
-  if ((pk.C & 3) == 0 && ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15u) == 0) {
-    const int w4 = width >> 2, nv4 = nvalid >> 2;
-    const float inv4 = 1.f / (float)w4;
-    for (int e = threadIdx.x; e < kr * w4; e += 256) {
-      const int row = (int)fdiv((uint32_t)e, (uint32_t)w4, inv4), j4 = e - row * w4;
-      const int64_t k = k0 + row;
-      uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0;
-      if (k < pk.K && j4 < nv4) {
-        const int64_t i = (k * pk.C + c0) * RS + 4 * j4;
-        float4 pv = *(float4*)(p + i), mv = *(float4*)(m + i), vv = *(float4*)(v + i);
-        const float4 gv = *(const float4*)(g + i);
-        adamw_update(pv.x, gv.x, mv.x, vv.x, s.h, s.step_size, s.bc2_sqrt);
-        adamw_update(pv.y, gv.y, mv.y, vv.y, s.h, s.step_size, s.bc2_sqrt);
-        adamw_update(pv.z, gv.z, mv.z, vv.z, s.h, s.step_size, s.bc2_sqrt);
-        adamw_update(pv.w, gv.w, mv.w, vv.w, s.h, s.step_size, s.bc2_sqrt);
-        *(float4*)(p + i) = pv;
-        *(float4*)(m + i) = mv;
-        *(float4*)(v + i) = vv;
-        o0 = hilo_word(pv.x); o1 = hilo_word(pv.y); o2 = hilo_word(pv.z); o3 = hilo_word(pv.w);
-      }
-      uint32_t* d = T + row * ldt + 4 * j4;
-      d[0] = o0; d[1] = o1; d[2] = o2; d[3] = o3;
-    }
-  } else {
-    const float inv = 1.f / (float)width;
-    for (int e = threadIdx.x; e < kr * width; e += 256) {
-      const int row = (int)fdiv((uint32_t)e, (uint32_t)width, inv), j = e - row * width;
-      const int64_t k = k0 + row;
-      uint32_t o = 0;
-      if (k < pk.K && j < nvalid) {
-        const int64_t i = (k * pk.C + c0) * RS + j;
-        float pv = p[i], mv = m[i], vv = v[i];
-        adamw_update(pv, g[i], mv, vv, s.h, s.step_size, s.bc2_sqrt);
-        p[i] = pv;
-        m[i] = mv;
-        v[i] = vv;
-        o = hilo_word(pv);
-      }
-      T[row * ldt + j] = o;
-    }
-  }
-  __syncthreads();
-  tile_store_layouts(pk, kr, tc, k0, c0, T, ldt);
-}
-
-__global__ void __launch_bounds__(256) adamw_pack_kernel(const AdamwJob* __restrict__ jobs,
-                                                         const int64_t* __restrict__ prefix,
-                                                         const float* const* __restrict__ grads, int njobs,
-                                                         AdamwStep s) {
-  extern __shared__ uint32_t Tsm[];
-  const int64_t bidx = blockIdx.x;
-  int lo = 0, hi = njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (prefix[mid] <= bidx) lo = mid; else hi = mid - 1;
-  }
-  const AdamwJob J = jobs[lo];
-  if (J.fused) adamw_pack_tile(J, grads[lo], bidx - prefix[lo], s, Tsm);
-  else adamw_plain_block(J, grads[lo], bidx - prefix[lo], s);
-}
-
-// Host: tile sizes of one pack job (both tile kinds fit PACK_LDS, rows padded by 4 elements)
-static int pack_plan(PackP& p) {
-  const int RS = p.R * p.S;
-  if (RS > 196) return MX_EINVAL;
-  p.tct = RS == 1 ? 64 : (RS <= 9 ? 32 : ((392 / RS) & ~3));  // multiples of 4: float4 staging
-  if (p.tct < 2) p.tct = 2;
-  int64_t cw = p.Cpad;
-  if (cw * RS + 4 > PACK_LDS) cw = ((PACK_LDS - 4) / RS) & ~3ll;
-  p.cw = (int)cw;
-  int64_t kr = 12288 / (cw * RS);
-  if (kr > 64) kr = 64;
-  while (kr > 1 && kr * (cw * RS + 4) > PACK_LDS) --kr;
-  if (kr < 1) kr = 1;
-  p.kr = (int)kr;
-  p.nwk = p.wk ? cdiv(p.K, p.kr) * cdiv(p.Cpad, p.cw) : 0;
-  p.nwt = p.wt ? cdiv(p.Kpad, (int64_t)PK) * cdiv(p.Cpad, (int64_t)p.tct) : 0;
-  p.wk_plane = p.K * RS * p.Cpad;
-  p.wt_plane = p.Cpad * RS * p.Kpad;
-  return MX_OK;
-}
-
 // KRSC bf16 weight -> the dgrad parity-class layout of pack_weight_kernel (element-wise; used by
 // the convenience mx_conv2d_dgrad only)
 __global__ void krsc_to_dgrad_kernel(const uint16_t* __restrict__ w, PackP p) {
@@ -3262,45 +2756,6 @@ static int launch_kind(const Cfg& cf, const Geo& g) {
   return c4 < c3 ? 4 : 3;
 }
 
-// dgrad stride-parity classes. dx(h) receives dy((h + pad - r) / st) only from taps with
-// r = (h + pad) mod st, so the rows with h = st*hh + ph form an independent dense GEMM over the
-// taps r = r0 + st*ri (r0 = (ph + pad) mod st): dx[n, st*hh+ph] = sum dy[n, hh + dh - ri] w_t[ri],
-// dh = (ph + pad - r0) / st. The classes partition both dx and the taps; wt stores each tap-parity
-// class's [C][Rc][Sc][K] block contiguously (block index = tap parity r0*st_w + s0).
-struct DClass {
-  int ph, pw, r0, s0, Rc, Sc, dh, dw;
-  int64_t Hc, Wc, off;
-};
-static int tap_count(int R, int r0, int st) { return r0 < R ? (R - r0 + st - 1) / st : 0; }
-static int dgrad_classes(const mx_conv_shape* s, int64_t Cpad, int64_t Kpad, DClass* out, int64_t* blk_off,
-                         int* blk_R, int* blk_S) {
-  const int sh = s->stride_h, sw = s->stride_w;
-  // block offsets by tap parity
-  int64_t off = 0;
-  for (int a = 0; a < sh; ++a)
-    for (int b = 0; b < sw; ++b) {
-      const int q = a * sw + b;
-      blk_R[q] = tap_count((int)s->R, a, sh);
-      blk_S[q] = tap_count((int)s->S, b, sw);
-      blk_off[q] = off;
-      off += Cpad * blk_R[q] * blk_S[q] * Kpad;
-    }
-  int n = 0;
-  for (int ph = 0; ph < sh; ++ph)
-    for (int pw = 0; pw < sw; ++pw) {
-      DClass c;
-      c.ph = ph; c.pw = pw;
-      c.r0 = (ph + s->pad_h) % sh; c.s0 = (pw + s->pad_w) % sw;
-      const int q = c.r0 * sw + c.s0;
-      c.Rc = blk_R[q]; c.Sc = blk_S[q]; c.off = blk_off[q];
-      c.dh = (ph + s->pad_h - c.r0) / sh; c.dw = (pw + s->pad_w - c.s0) / sw;
-      c.Hc = ph < s->H ? (s->H - ph + sh - 1) / sh : 0;
-      c.Wc = pw < s->W ? (s->W - pw + sw - 1) / sw : 0;
-      out[n++] = c;
-    }
-  return n;
-}
-
 static size_t wgrad_ws(const Cfg& cf, const mx_conv_shape* s);
 
 extern "C" size_t mx_conv_workspace(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg) {
@@ -3460,224 +2915,6 @@ extern "C" int mx_conv_transpose_weight(const uint16_t* w, int64_t K, int64_t RS
 extern "C" size_t mx_conv_dgrad_weight_elems(const mx_conv_shape* s, int64_t Cpad, int64_t Kpad) {
   if (!s) return 0;
   return (size_t)(Cpad ? Cpad : s->C) * s->R * s->S * (Kpad ? Kpad : s->K);
-}
-
-extern "C" int mx_conv_pack_weight(const mx_conv_shape* s, const float* w, int64_t Cin, int64_t Kout, uint16_t* wk,
-                                   uint16_t* wt, int split, mx_stream_t stream) {
-  // s->C / s->K are the padded channel counts the kernels see (Cin <= s->C real input channels,
-  // Kout <= s->K real output channels of the f32 parameter w[Kout][Cin][R][S])
-  MX_CHECK_ARG(s && w && s->R > 0 && s->S > 0 && Cin > 0 && Kout > 0 && Cin <= s->C && Kout <= s->K,
-               "conv pack: bad shape");
-  MX_CHECK_ARG(!wt || (s->stride_h >= 1 && s->stride_h <= 2 && s->stride_w >= 1 && s->stride_w <= 2),
-               "conv pack: dgrad layout supports strides 1 and 2");
-  if (!wk && !wt) return MX_OK;
-  PackP p{};
-  p.w = w; p.wk = wk; p.wt = wt;
-  p.K = Kout; p.C = Cin; p.Cpad = s->C; p.Kpad = s->K;
-  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w;
-  if (wt) {
-    DClass cl[4];
-    dgrad_classes(s, s->C, s->K, cl, p.off, p.Rc, p.Sc);
-  } else {
-    p.st_h = p.st_w = 1;
-  }
-  // wk covers Kout rows only; wt also covers the zero-padded output channels up to s->K
-  MX_CHECK_ARG(pack_plan(p) == MX_OK, "conv pack: at most 196 taps");
-  p.split = split ? 1 : 0;
-  const int64_t tiles = p.nwk + p.nwt;
-  MX_CHECK_ARG(tiles < (1ll << 31), "conv pack: too many tiles");
-  pack_weight_kernel<<<(unsigned)tiles, 256, 0, (hipStream_t)stream>>>(p);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
-}
-
-static int make_pack(const mx_pack_desc& d, PackP& p, int64_t& tiles) {
-  MX_CHECK_ARG(d.w && d.R > 0 && d.S > 0 && d.Cin > 0 && d.Kout > 0 && d.Cin <= d.Cpad && d.Kout <= d.Kpad,
-               "conv pack: bad job");
-  MX_CHECK_ARG(!d.wt || (d.stride_h >= 1 && d.stride_h <= 2 && d.stride_w >= 1 && d.stride_w <= 2),
-               "conv pack: dgrad layout supports strides 1 and 2");
-  p = PackP{};
-  p.w = d.w; p.wk = d.wk; p.wt = d.wt;
-  p.K = d.Kout; p.C = d.Cin; p.Cpad = d.Cpad; p.Kpad = d.Kpad;
-  p.R = d.R; p.S = d.S; p.st_h = d.stride_h; p.st_w = d.stride_w;
-  p.dense = d.flags & 1;
-  p.split = (d.flags >> 1) & 1;
-  if (d.wt && !p.dense) {
-    mx_conv_shape s{};
-    s.C = d.Cpad; s.K = d.Kpad; s.R = d.R; s.S = d.S; s.H = 1; s.W = 1;
-    s.stride_h = d.stride_h; s.stride_w = d.stride_w; s.pad_h = d.pad_h; s.pad_w = d.pad_w;
-    DClass cl[4];
-    dgrad_classes(&s, d.Cpad, d.Kpad, cl, p.off, p.Rc, p.Sc);
-  } else {
-    p.st_h = p.st_w = 1;
-  }
-  MX_CHECK_ARG(pack_plan(p) == MX_OK, "conv pack: at most 196 taps");
-  tiles = p.nwk + p.nwt;
-  return MX_OK;
-}
-
-extern "C" size_t mx_conv_pack_plan_bytes(int64_t njobs) {
-  return njobs > 0 ? sizeof(PackP) * (size_t)njobs + sizeof(int64_t) * (size_t)(njobs + 1) : 0;
-}
-
-extern "C" int mx_conv_pack_batched(const mx_pack_desc* jobs, int64_t njobs, void* plan, size_t plan_bytes, int upload,
-                                    mx_stream_t stream) {
-  MX_CHECK_ARG(jobs && njobs > 0 && njobs < (1 << 20), "conv pack batched: bad job list");
-  MX_CHECK_ARG(plan && plan_bytes >= mx_conv_pack_plan_bytes(njobs), "conv pack batched: plan buffer too small");
-  std::vector<PackP> host((size_t)njobs);
-  std::vector<int64_t> prefix((size_t)njobs + 1, 0);
-  for (int64_t j = 0; j < njobs; ++j) {
-    int64_t t = 0;
-    int rc = make_pack(jobs[j], host[(size_t)j], t);
-    if (rc) return rc;
-    if (!jobs[j].wk && !jobs[j].wt) t = 0;
-    prefix[(size_t)j + 1] = prefix[(size_t)j] + t;
-  }
-  const int64_t total = prefix[(size_t)njobs];
-  MX_CHECK_ARG(total < (1ll << 31), "conv pack batched: too many tiles");
-  hipStream_t st = (hipStream_t)stream;
-  PackP* dj = (PackP*)plan;
-  int64_t* dp = (int64_t*)((char*)plan + sizeof(PackP) * (size_t)njobs);
-  if (upload) {
-    // the host vectors die with this call: synchronous copies (the plan changes rarely)
-    MX_HIP(hipStreamSynchronize(st));
-    MX_HIP(hipMemcpy(dj, host.data(), sizeof(PackP) * (size_t)njobs, hipMemcpyHostToDevice));
-    MX_HIP(hipMemcpy(dp, prefix.data(), sizeof(int64_t) * (size_t)(njobs + 1), hipMemcpyHostToDevice));
-  }
-  if (total == 0) return MX_OK;
-  pack_batched_kernel<<<(unsigned)total, 256, 0, st>>>(dj, dp, (int)njobs);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
-}
-
-// fused tile for R*S taps (sgd_pack_tile): 64x64 (1x1), 32x32 (<= 9 taps), 16x8 (<= 49 taps; FC6).
-// One launch reserves the largest tile's LDS for every block: FC6's 16x16 (50 KiB) held the whole
-// launch to 3 blocks per CU; 16x8 (25 KiB) leaves the 3x3 tile (37 KiB) as the bound (4 per CU).
-static bool sgd_tile(int RS, int& kr, int& tc) {
-  if (RS == 1) { kr = 64; tc = 64; return true; }
-  if (RS <= 9) { kr = 32; tc = 32; return true; }
-  if (RS <= 49) { kr = 16; tc = 8; return true; }
-  return false;
-}
-
-// One fused job of mx_sgd_pack_build / mx_adamw_pack_build (`who` in the messages): parameter j (p, n
-// elements) as packs[pack] -> its PackP, tile, channel blocks per row block, block count; lds grows
-// to the tile's (hi, lo) words, rows padded by one
-static int fused_job(const char* who, const mx_pack_desc* packs, int32_t pack, int64_t j, const float* p, int64_t n,
-                     PackP& pk, int& kr, int& tc, int64_t& ncb, int64_t& nb, size_t& lds) {
-  MX_CHECK_ARG(packs, "%s pack build: pack index without pack list", who);
-  const mx_pack_desc& d = packs[pack];
-  int64_t tiles = 0;
-  int rc = make_pack(d, pk, tiles);
-  if (rc) return rc;
-  const int RS = d.R * d.S;
-  MX_CHECK_ARG(d.w == p && d.Kout * d.Cin * RS == n, "%s pack build: pack %lld is not parameter %lld", who,
-               (long long)pack, (long long)j);
-  MX_CHECK_ARG(sgd_tile(RS, kr, tc), "%s pack build: %d taps (fused packing takes <= 49)", who, RS);
-  MX_CHECK_ARG(d.wk || d.wt, "%s pack build: pack %lld has no layout", who, (long long)pack);
-  ncb = cdiv(pk.Cpad, tc);
-  nb = cdiv(pk.Kpad, kr) * ncb;
-  const size_t need = sizeof(uint32_t) * (size_t)kr * (size_t)(tc * RS + 1);
-  if (need > lds) lds = need;
-  return MX_OK;
-}
-
-extern "C" size_t mx_sgd_pack_plan_bytes(int64_t nparams) {
-  return nparams > 0 ? sizeof(SgdJob) * (size_t)nparams + sizeof(int64_t) * (size_t)(nparams + 1) : 0;
-}
-
-extern "C" int mx_sgd_pack_build(const mx_sgd_param* params, int64_t nparams, const mx_pack_desc* packs,
-                                 void* host_plan, size_t plan_bytes, int64_t* blocks, size_t* lds_bytes) {
-  MX_CHECK_ARG(params && nparams > 0 && nparams < (1 << 20) && blocks && lds_bytes, "sgd pack build: bad lists");
-  MX_CHECK_ARG(host_plan && plan_bytes >= mx_sgd_pack_plan_bytes(nparams), "sgd pack build: plan buffer too small");
-  SgdJob* jobs = (SgdJob*)host_plan;
-  int64_t* prefix = (int64_t*)((char*)host_plan + sizeof(SgdJob) * (size_t)nparams);
-  prefix[0] = 0;
-  size_t lds = 0;
-  for (int64_t j = 0; j < nparams; ++j) {
-    const mx_sgd_param& q = params[j];
-    MX_CHECK_ARG(q.p && q.buf && q.n > 0, "sgd pack build: parameter %lld empty or null", (long long)j);
-    SgdJob J{};
-    J.p = q.p; J.b = q.buf; J.n = q.n; J.first = q.first ? 1 : 0;
-    int64_t nb = cdiv(q.n, SGDP_PER_BLOCK);
-    if (q.pack >= 0) {
-      int rc = fused_job("sgd", packs, q.pack, j, q.p, q.n, J.pk, J.kr, J.tc, J.ncb, nb, lds);
-      if (rc) return rc;
-      J.fused = 1;
-    }
-    jobs[j] = J;
-    prefix[j + 1] = prefix[j] + nb;
-  }
-  MX_CHECK_ARG(prefix[nparams] < (1ll << 31), "sgd pack build: too many blocks");
-  *blocks = prefix[nparams];
-  *lds_bytes = lds;
-  return MX_OK;
-}
-
-extern "C" int mx_sgd_pack_step(const void* plan, const float* const* grads, int64_t nparams, int64_t blocks,
-                                size_t lds_bytes, float lr, float momentum, float dampening, float weight_decay,
-                                int nesterov, mx_stream_t stream) {
-  MX_CHECK_ARG(plan && grads && nparams > 0 && blocks > 0 && blocks < (1ll << 31) && lds_bytes <= 65536,
-               "sgd pack step: bad plan");
-  const SgdJob* jobs = (const SgdJob*)plan;
-  const int64_t* prefix = (const int64_t*)((const char*)plan + sizeof(SgdJob) * (size_t)nparams);
-  SgdHyper h{lr, momentum, dampening, weight_decay, nesterov};
-  sgd_pack_kernel<<<(unsigned)blocks, 256, lds_bytes, (hipStream_t)stream>>>(jobs, prefix, grads, (int)nparams, h);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
-}
-
-extern "C" size_t mx_adamw_pack_plan_bytes(int64_t nparams) {
-  return nparams > 0 ? sizeof(AdamwJob) * (size_t)nparams + sizeof(int64_t) * (size_t)(nparams + 1) : 0;
-}
-
-// the conventions and the tile choice (fused_job, sgd_tile) of mx_sgd_pack_build
-extern "C" int mx_adamw_pack_build(const mx_adamw_param* params, int64_t nparams, const mx_pack_desc* packs,
-                                   void* host_plan, size_t plan_bytes, int64_t* blocks, size_t* lds_bytes) {
-  MX_CHECK_ARG(params && nparams > 0 && nparams < (1 << 20) && blocks && lds_bytes, "adamw pack build: bad lists");
-  MX_CHECK_ARG(host_plan && plan_bytes >= mx_adamw_pack_plan_bytes(nparams), "adamw pack build: plan buffer too small");
-  AdamwJob* jobs = (AdamwJob*)host_plan;
-  int64_t* prefix = (int64_t*)((char*)host_plan + sizeof(AdamwJob) * (size_t)nparams);
-  prefix[0] = 0;
-  size_t lds = 0;
-  for (int64_t j = 0; j < nparams; ++j) {
-    const mx_adamw_param& q = params[j];
-    MX_CHECK_ARG(q.p && q.exp_avg && q.exp_avg_sq && q.n > 0, "adamw pack build: parameter %lld empty or null",
-                 (long long)j);
-    MX_CHECK_ARG(q.reserved == 0, "adamw pack build: parameter %lld has reserved != 0", (long long)j);
-    AdamwJob J{};
-    J.p = q.p; J.m = q.exp_avg; J.v = q.exp_avg_sq; J.n = q.n;
-    int64_t nb = cdiv(q.n, SGDP_PER_BLOCK);
-    if (q.pack >= 0) {
-      int rc = fused_job("adamw", packs, q.pack, j, q.p, q.n, J.pk, J.kr, J.tc, J.ncb, nb, lds);
-      if (rc) return rc;
-      J.fused = 1;
-    }
-    jobs[j] = J;
-    prefix[j + 1] = prefix[j] + nb;
-  }
-  MX_CHECK_ARG(prefix[nparams] < (1ll << 31), "adamw pack build: too many blocks");
-  *blocks = prefix[nparams];
-  *lds_bytes = lds;
-  return MX_OK;
-}
-
-extern "C" int mx_adamw_pack_step(const void* plan, const float* const* grads, int64_t nparams, int64_t blocks,
-                                  size_t lds_bytes, int64_t step, double lr, double beta1, double beta2, double eps,
-                                  double weight_decay, mx_stream_t stream) {
-  MX_CHECK_ARG(plan && grads && nparams > 0 && blocks > 0 && blocks < (1ll << 31) && lds_bytes <= 65536,
-               "adamw pack step: bad plan");
-  MX_CHECK_ARG(step >= 1, "adamw pack step: step %lld (the step number after this step, >= 1)", (long long)step);
-  MX_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adamw pack step: betas outside [0, 1)");
-  MX_CHECK_ARG(eps >= 0.0, "adamw pack step: negative eps");
-  const AdamwJob* jobs = (const AdamwJob*)plan;
-  const int64_t* prefix = (const int64_t*)((const char*)plan + sizeof(AdamwJob) * (size_t)nparams);
-  AdamwStep s{};
-  s.h = adamw_hyper(lr, beta1, beta2, eps, weight_decay);
-  adamw_bias(lr, beta1, beta2, step, s.step_size, s.bc2_sqrt);
-  adamw_pack_kernel<<<(unsigned)blocks, 256, lds_bytes, (hipStream_t)stream>>>(jobs, prefix, grads, (int)nparams, s);
-  MX_LAUNCH_CHECK();
-  return MX_OK;
 }
 
 // dgrad with the weight packed by mx_conv_pack_weight (for stride 1 that layout is the plain

@@ -6,12 +6,13 @@
 //   d = nesterov ? d + momentum * buf : buf;  p -= lr * d
 // Replaces the three multi_tensor_apply launches (plus their host-side grouping) of torch's foreach
 // path with one streaming pass: 20 B of HBM traffic per parameter (p, g, buf read; p, buf written).
+// The element updates, the update rules and the streaming body (update_chunk) are in mx_common.h,
+// shared with the forms fused with the conv operand pack (mx_pack.hip).
 #include "mx_common.h"
 
 namespace mx {
 
-static constexpr int SGD_CHUNK = 64;      // tensors per launch (kernel-argument struct < 4 KiB)
-static constexpr int SGD_PER_BLOCK = 2048; // elements per 256-thread block
+static constexpr int SGD_CHUNK = 64;  // tensors per launch (kernel-argument struct < 4 KiB)
 
 struct SgdArgs {
   float* p[SGD_CHUNK];
@@ -21,47 +22,15 @@ struct SgdArgs {
   int32_t first_block[SGD_CHUNK + 1];  // prefix of blocks per tensor
   uint64_t first_mask;                 // bit t: tensor t takes its first momentum step
   int count;
-  float lr, momentum, dampening, wd;
-  int nesterov;
+  SgdHyper h;
 };
 
-__device__ __forceinline__ float sgd1(float& p, float g, float& b, bool first, const SgdArgs& a) {
-  return sgd_update(p, g, b, first, a.lr, a.momentum, a.dampening, a.wd, a.nesterov);
-}
-
+// block -> tensor t with first_block[t] <= block < first_block[t + 1], then its chunk of t
 __global__ void __launch_bounds__(256) sgd_kernel(SgdArgs a) {
-  const int blk = blockIdx.x;
-  int lo = 0, hi = a.count - 1;  // tensor t with first_block[t] <= blk < first_block[t+1]
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.first_block[mid] <= blk) lo = mid;
-    else hi = mid - 1;
-  }
-  const int t = lo;
-  const int64_t n = a.n[t];
-  const int64_t e0 = (int64_t)(blk - a.first_block[t]) * SGD_PER_BLOCK;
-  const int64_t e1 = min<int64_t>(n, e0 + SGD_PER_BLOCK);
-  float* __restrict__ p = a.p[t];
-  const float* __restrict__ g = a.g[t];
-  float* __restrict__ b = a.buf[t];
-  const bool first = (a.first_mask >> t) & 1ull;
-  const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)b)) & 15u) == 0;
-  if (vec) {
-    for (int64_t e = e0 + threadIdx.x * 4; e + 3 < e1; e += 256 * 4) {
-      float4 pv = *(float4*)(p + e), bv = *(float4*)(b + e);
-      const float4 gv = *(const float4*)(g + e);
-      sgd1(pv.x, gv.x, bv.x, first, a);
-      sgd1(pv.y, gv.y, bv.y, first, a);
-      sgd1(pv.z, gv.z, bv.z, first, a);
-      sgd1(pv.w, gv.w, bv.w, first, a);
-      *(float4*)(p + e) = pv;
-      *(float4*)(b + e) = bv;
-    }
-    const int64_t tail = e0 + ((e1 - e0) & ~(int64_t)3);
-    for (int64_t e = tail + threadIdx.x; e < e1; e += 256) sgd1(p[e], g[e], b[e], first, a);
-  } else {
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) sgd1(p[e], g[e], b[e], first, a);
-  }
+  const int t = last_job(a.first_block, a.count, blockIdx.x);
+  float* const s[1] = {a.buf[t]};
+  update_chunk<SgdRule>(a.p[t], a.g[t], s, a.n[t], blockIdx.x - a.first_block[t], a.h,
+                        SgdRule::Tensor{(int)((a.first_mask >> t) & 1ull)});
 }
 
 // torch.optim.AdamW (the reference: AdamW(lr=1e-3, weight_decay=1e-4), train_restoration.py:246, step
@@ -85,39 +54,10 @@ struct AdamwArgs {
 static_assert(sizeof(AdamwArgs) <= 4096, "kernel-argument struct");
 
 __global__ void __launch_bounds__(256) adamw_kernel(AdamwArgs a) {
-  const int blk = blockIdx.x;
-  int lo = 0, hi = a.count - 1;  // tensor t with first_block[t] <= blk < first_block[t+1]
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (a.first_block[mid] <= blk) lo = mid;
-    else hi = mid - 1;
-  }
-  const int t = lo;
-  const int64_t e0 = (int64_t)(blk - a.first_block[t]) * SGD_PER_BLOCK;
-  const int64_t e1 = min<int64_t>(a.n[t], e0 + SGD_PER_BLOCK);
-  float* __restrict__ p = a.p[t];
-  const float* __restrict__ g = a.g[t];
-  float* __restrict__ m = a.m[t];
-  float* __restrict__ v = a.v[t];
-  const float ss = a.step_size[t], bc = a.bc2_sqrt[t];
-  const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15u) == 0;
-  if (vec) {
-    for (int64_t e = e0 + threadIdx.x * 4; e + 3 < e1; e += 256 * 4) {
-      float4 pv = *(float4*)(p + e), mv = *(float4*)(m + e), vv = *(float4*)(v + e);
-      const float4 gv = *(const float4*)(g + e);
-      adamw_update(pv.x, gv.x, mv.x, vv.x, a.h, ss, bc);
-      adamw_update(pv.y, gv.y, mv.y, vv.y, a.h, ss, bc);
-      adamw_update(pv.z, gv.z, mv.z, vv.z, a.h, ss, bc);
-      adamw_update(pv.w, gv.w, mv.w, vv.w, a.h, ss, bc);
-      *(float4*)(p + e) = pv;
-      *(float4*)(m + e) = mv;
-      *(float4*)(v + e) = vv;
-    }
-    const int64_t tail = e0 + ((e1 - e0) & ~(int64_t)3);
-    for (int64_t e = tail + threadIdx.x; e < e1; e += 256) adamw_update(p[e], g[e], m[e], v[e], a.h, ss, bc);
-  } else {
-    for (int64_t e = e0 + threadIdx.x; e < e1; e += 256) adamw_update(p[e], g[e], m[e], v[e], a.h, ss, bc);
-  }
+  const int t = last_job(a.first_block, a.count, blockIdx.x);
+  float* const s[2] = {a.m[t], a.v[t]};
+  update_chunk<AdamwRule>(a.p[t], a.g[t], s, a.n[t], blockIdx.x - a.first_block[t], a.h,
+                          AdamwRule::Tensor{a.step_size[t], a.bc2_sqrt[t]});
 }
 
 }  // namespace mx
@@ -131,7 +71,7 @@ extern "C" int mx_sgd_step(float* const* params, const float* const* grads, floa
   for (int64_t c0 = 0; c0 < count; c0 += SGD_CHUNK) {
     SgdArgs a{};
     a.count = (int)std::min<int64_t>(SGD_CHUNK, count - c0);
-    a.lr = lr; a.momentum = momentum; a.dampening = dampening; a.wd = weight_decay; a.nesterov = nesterov;
+    a.h = SgdHyper{lr, momentum, dampening, weight_decay, nesterov};
     int64_t blocks = 0;
     for (int i = 0; i < a.count; ++i) {
       const int64_t j = c0 + i;
@@ -139,7 +79,7 @@ extern "C" int mx_sgd_step(float* const* params, const float* const* grads, floa
       a.p[i] = params[j]; a.g[i] = grads[j]; a.buf[i] = bufs[j]; a.n[i] = numels[j];
       if (first[j]) a.first_mask |= 1ull << i;
       a.first_block[i] = (int32_t)blocks;
-      blocks += cdiv(numels[j], SGD_PER_BLOCK);
+      blocks += cdiv(numels[j], UPDATE_PER_BLOCK);
       MX_CHECK_ARG(blocks < (1ll << 31), "sgd_step: too many elements");
     }
     a.first_block[a.count] = (int32_t)blocks;
@@ -173,7 +113,7 @@ extern "C" int mx_adamw_step(float* const* params, const float* const* grads, fl
       a.p[i] = params[j]; a.g[i] = grads[j]; a.m[i] = exp_avgs[j]; a.v[i] = exp_avg_sqs[j]; a.n[i] = numels[j];
       adamw_bias(lr, beta1, beta2, steps[j], a.step_size[i], a.bc2_sqrt[i]);
       a.first_block[i] = (int32_t)blocks;
-      blocks += cdiv(numels[j], SGD_PER_BLOCK);
+      blocks += cdiv(numels[j], UPDATE_PER_BLOCK);
       MX_CHECK_ARG(blocks < (1ll << 31), "adamw_step: too many elements");
     }
     a.first_block[a.count] = (int32_t)blocks;

@@ -19,6 +19,7 @@ from torch.optim.adam import adam as _torch_adam
 from torch.optim.optimizer import _get_scalar_dtype, _use_grad_for_differentiable
 
 from . import _lib
+from . import conv as mc
 
 
 # MX_SGD_PACK=0: keep the update and the conv operand repack as two launches (sgd_kernel, then
@@ -30,9 +31,34 @@ _SGD_PACK = int(os.environ.get("MX_SGD_PACK", "1"))
 _ADAMW_PACK = int(os.environ.get("MX_ADAMW_PACK", "1"))
 
 
-def mc_PackDesc():
-    from .conv import PackDesc
-    return PackDesc
+def _f32_dense(t):
+    return t.is_cuda and t.dtype == torch.float32 and not t.is_sparse and t.is_contiguous()
+
+
+def _fused_plan(prefix, prm, entries, pk, device):
+    """The device plan of a fused launch, built by the entries `prefix`_plan_bytes / `prefix`_build
+    ("mx_sgd_pack", "mx_adamw_pack") from the filled parameter table prm, whose pack indices count the
+    entries that are not None in order. Returns plan, blocks, lds (the step entry's arguments)."""
+    packs = [e for e in entries if e is not None]
+    descs = (mc.PackDesc * len(packs))(*[pk.desc(e) for e in packs])
+    n = len(prm)
+    nb = getattr(_lib.load(), prefix + "_plan_bytes")(n)
+    host = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+    blocks, lds = ctypes.c_int64(0), ctypes.c_size_t(0)
+    _lib.call(prefix + "_build", prm, n, descs, host.data_ptr(), nb, ctypes.byref(blocks), ctypes.byref(lds))
+    return host.to(device, non_blocking=True), blocks.value, lds.value
+
+
+def _grad_table(c, grads, device):
+    """c["gdev"], the device table of the gradients' pointers: uploaded again when they differ from
+    c["gkey"]. False when a gradient is not f32 / dense / contiguous / CUDA."""
+    gptr = [g.data_ptr() for g in grads]
+    if gptr != c["gkey"]:
+        if not all(_f32_dense(g) for g in grads):
+            return False
+        c["gdev"] = torch.tensor(gptr, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+        c["gkey"] = gptr
+    return True
 
 
 class _SgdParam(ctypes.Structure):  # mx_sgd_param
@@ -61,8 +87,7 @@ class SGD(torch.optim.SGD):
             if not ps:
                 continue
             if (group.get("maximize") or group["momentum"] == 0 or
-                    any(not p.is_cuda or p.dtype != torch.float32 or p.grad.is_sparse or
-                        not p.is_contiguous() or not p.grad.is_contiguous() for p in ps)):
+                    any(not _f32_dense(p) or p.grad.is_sparse or not p.grad.is_contiguous() for p in ps)):
                 self._torch_step(group, ps)
                 continue
             n = len(ps)
@@ -86,9 +111,9 @@ class SGD(torch.optim.SGD):
             increment_version(ps)
             increment_version(bufs)
             if len(ps) == len(group["params"]):  # all present: cache the static arrays for _fast_step
-                self.__dict__.setdefault("_fast", {})[id(group)] = (
-                    group["params"], n, P, B, N, (ctypes.c_uint8 * n)(), bufs, [p.data_ptr() for p in ps],
-                    [b.data_ptr() for b in bufs])
+                fast[id(group)] = {"ps": group["params"], "n": n, "P": P, "B": B, "N": N,
+                                   "first": (ctypes.c_uint8 * n)(), "bufs": bufs,
+                                   "pptr": [p.data_ptr() for p in ps], "bptr": [b.data_ptr() for b in bufs]}
         return loss
 
     def _pack_step(self, group):
@@ -98,7 +123,6 @@ class SGD(torch.optim.SGD):
         other paths (no packer, nothing to fold, or a case the multi-tensor kernel does not cover).
         Steady state (same parameters, buffers and packer): only the gradients' pointers are gathered
         on the host; the device plan is rebuilt when anything else changes."""
-        from . import conv as mc
         pk = mc.get_packer()
         if pk is None or _SGD_PACK == 0:
             return False
@@ -115,20 +139,15 @@ class SGD(torch.optim.SGD):
                 c = None
         if c is None or c["ps"] is not ps or c["packer"] is not pk or not c["ready"]:
             if (not ps or group.get("maximize") or group["momentum"] == 0 or
-                    any(p.grad is None or not p.is_cuda or p.dtype != torch.float32 or p.grad.is_sparse or
-                        not p.is_contiguous() for p in ps)):
+                    any(p.grad is None or not _f32_dense(p) or p.grad.is_sparse for p in ps)):
                 return False
             c = self._pack_plan(group, pk)
             if c is None:
                 return False
             cache[id(group)] = c
             grads = [p.grad for p in ps]
-        gptr = [g.data_ptr() for g in grads]
-        if gptr != c["gkey"]:
-            if any(not g.is_contiguous() or g.dtype != torch.float32 or g.is_sparse or not g.is_cuda for g in grads):
-                return False
-            c["gdev"] = torch.tensor(gptr, dtype=torch.int64).pin_memory().to(ps[0].device, non_blocking=True)
-            c["gkey"] = gptr
+        if not _grad_table(c, grads, ps[0].device):
+            return False
         _lib.call("mx_sgd_pack_step", c["plan"].data_ptr(), c["gdev"].data_ptr(), len(ps), c["blocks"], c["lds"],
                   float(group["lr"]), float(group["momentum"]), float(group["dampening"]),
                   float(group["weight_decay"]), int(group["nesterov"]), _lib.stream())
@@ -158,23 +177,16 @@ class SGD(torch.optim.SGD):
             else:
                 first.append(0)
             bufs.append(b)
-        packs = [e for e in entries if e is not None]
-        descs = (mc_PackDesc() * len(packs))(*[pk.desc(e) for e in packs])
         prm = (_SgdParam * n)()
         j = 0
         for i, (p, b, e) in enumerate(zip(ps, bufs, entries)):
             prm[i] = _SgdParam(p.data_ptr(), b.data_ptr(), p.numel(), first[i], j if e is not None else -1)
             j += e is not None
-        lib = _lib.load()
-        nb = lib.mx_sgd_pack_plan_bytes(n)
-        host = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
-        blocks, lds = ctypes.c_int64(0), ctypes.c_size_t(0)
-        _lib.call("mx_sgd_pack_build", prm, n, descs, host.data_ptr(), nb, ctypes.byref(blocks), ctypes.byref(lds))
+        plan, blocks, lds = _fused_plan("mx_sgd_pack", prm, entries, pk, ps[0].device)
         for p, b in fresh.items():
             self.state[p]["momentum_buffer"] = b
         return {"ps": ps, "packer": pk, "pptr": [p.data_ptr() for p in ps], "entries": entries, "bufs": bufs,
-                "first": first, "ready": not any(first), "plan": host.to(ps[0].device, non_blocking=True),
-                "blocks": blocks.value, "lds": lds.value, "gkey": None}
+                "first": first, "ready": not any(first), "plan": plan, "blocks": blocks, "lds": lds, "gkey": None}
 
     def _fast_step(self, group, fast):
         """Steady state: every parameter of the group has a grad and a momentum buffer, and the
@@ -182,14 +194,14 @@ class SGD(torch.optim.SGD):
         (new tensors each step) are gathered. Returns False to take the general path."""
         ps = group["params"]
         c = fast.get(id(group))
-        if c is None or c[0] is not ps or c[1] != len(ps):
+        if c is None or c["ps"] is not ps or c["n"] != len(ps):
             fast.pop(id(group), None)
             return False
         # parameters and momentum buffers still the cached storage (p.data =, load_state_dict, ...)
         st = self.state
         bufs = [st[p].get("momentum_buffer") if p in st else None for p in ps]
-        if (any(b is None for b in bufs) or [p.data_ptr() for p in ps] != c[7]
-                or [b.data_ptr() for b in bufs] != c[8]):
+        if (any(b is None for b in bufs) or [p.data_ptr() for p in ps] != c["pptr"]
+                or [b.data_ptr() for b in bufs] != c["bptr"]):
             fast.pop(id(group), None)
             return False
         grads = [p.grad for p in ps]
@@ -197,10 +209,11 @@ class SGD(torch.optim.SGD):
             return False
         n = len(ps)
         G = (ctypes.c_void_p * n)(*[g.data_ptr() for g in grads])
-        _lib.call("mx_sgd_step", c[2], G, c[3], c[4], c[5], n, float(group["lr"]), float(group["momentum"]),
-                  float(group["dampening"]), float(group["weight_decay"]), int(group["nesterov"]), _lib.stream())
+        _lib.call("mx_sgd_step", c["P"], G, c["B"], c["N"], c["first"], n, float(group["lr"]),
+                  float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]),
+                  int(group["nesterov"]), _lib.stream())
         increment_version(ps)
-        increment_version(c[6])
+        increment_version(c["bufs"])
         return True
 
     def _torch_step(self, group, ps):
@@ -222,10 +235,6 @@ class SGD(torch.optim.SGD):
 class _AdamwParam(ctypes.Structure):  # mx_adamw_param
     _fields_ = [("p", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
                 ("n", ctypes.c_int64), ("pack", ctypes.c_int32), ("reserved", ctypes.c_int32)]
-
-
-def _f32_dense(t):
-    return t.is_cuda and t.dtype == torch.float32 and not t.is_sparse and t.is_contiguous()
 
 
 class AdamW(torch.optim.AdamW):
@@ -336,7 +345,6 @@ class AdamW(torch.optim.AdamW):
         parameters, state tensors and packer): only the gradients' pointers are gathered on the host;
         the device plan is rebuilt when anything else changes (load_state_dict, p.data = ...). The
         hyper-parameters are launch arguments, so an LR schedule rebuilds nothing."""
-        from . import conv as mc
         pk = mc.get_packer()
         if pk is None or _ADAMW_PACK == 0:
             return False
@@ -367,12 +375,8 @@ class AdamW(torch.optim.AdamW):
                 return False
             cache[id(group)] = c
             grads = [p.grad for p in ps]
-        gptr = [g.data_ptr() for g in grads]
-        if gptr != c["gkey"]:
-            if any(not _f32_dense(g) for g in grads):
-                return False
-            c["gdev"] = torch.tensor(gptr, dtype=torch.int64).pin_memory().to(ps[0].device, non_blocking=True)
-            c["gkey"] = gptr
+        if not _grad_table(c, grads, ps[0].device):
+            return False
         b1, b2 = group["betas"]
         _lib.call("mx_adamw_pack_step", c["plan"].data_ptr(), c["gdev"].data_ptr(), len(ps), c["blocks"], c["lds"],
                   c["step"] + 1, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
@@ -408,19 +412,12 @@ class AdamW(torch.optim.AdamW):
         if len(nums) != 1:  # one launch carries one step number
             return None
         ms, vs = [s["exp_avg"] for s in sts], [s["exp_avg_sq"] for s in sts]
-        packs = [e for e in entries if e is not None]
-        descs = (mc_PackDesc() * len(packs))(*[pk.desc(e) for e in packs])
         prm = (_AdamwParam * n)()
         j = 0
         for i, (p, m, v, e) in enumerate(zip(ps, ms, vs, entries)):
             prm[i] = _AdamwParam(p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), j if e is not None else -1, 0)
             j += e is not None
-        lib = _lib.load()
-        nb = lib.mx_adamw_pack_plan_bytes(n)
-        host = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
-        blocks, lds = ctypes.c_int64(0), ctypes.c_size_t(0)
-        _lib.call("mx_adamw_pack_build", prm, n, descs, host.data_ptr(), nb, ctypes.byref(blocks), ctypes.byref(lds))
+        plan, blocks, lds = _fused_plan("mx_adamw_pack", prm, entries, pk, ps[0].device)
         return {"ps": ps, "n": n, "packer": pk, "pptr": [p.data_ptr() for p in ps], "entries": entries, "ms": ms,
-                "vs": vs, "steps": steps, "step": nums.pop(), "fresh": fresh,
-                "plan": host.to(ps[0].device, non_blocking=True), "blocks": blocks.value, "lds": lds.value,
-                "gkey": None}
+                "vs": vs, "steps": steps, "step": nums.pop(), "fresh": fresh, "plan": plan, "blocks": blocks,
+                "lds": lds, "gkey": None}
