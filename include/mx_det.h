@@ -287,6 +287,45 @@ int mx_corrupt_batch_u8(const mx_corrupt_desc* descs_host, int64_t n, const floa
                         const float* noise, mx_stream_t stream);
 /* out[0], out[1] = rows, columns of the output tile one workgroup of mx_corrupt_batch_u8 owns. */
 int mx_corrupt_batch_tile(int32_t out[2]);
+/* Night, haze and rain for a whole batch in one launch (csrc/mx_weather.hip), each image with its own op,
+ * parameters and size; the launch scheme of mx_corrupt_batch_u8 (one workgroup per output tile of one
+ * image, descriptors as the kernel argument in chunks of 16 images: no workspace, no upload, no host
+ * synchronisation, no allocation, capturable in a graph). The ops are this project's own definitions;
+ * philox(counter x, y, z, w) below is Philox4x32-10 keyed (seed lo, seed hi), .x its first word.
+ *   op 1 night (f32, every op rounded once): for byte i (flat index within the image) with value v,
+ *     d = v * gain, s = sqrt(shot * d + read2), out = (u8)clip(d + s * g, 0, 255) (truncation), g =
+ *     noise[i] when the call passes a field, else the Box-Muller normal of philox(i lo, i hi, 0x5eed, 0)
+ *     that mx_corrupt_u8's noise uses.
+ *   op 2 haze (integers, every product < 2^32): octaves o = 0..3 with cell c = 256 >> o, s = 8 - o;
+ *     lattice L_o(j, i) = philox(i, j, 0x48415a45, o).x >> 16; for pixel (y, x): j = y >> s, i = x >> s,
+ *     fy = y & (c-1), fx = x & (c-1), top = L(j,i)*(c-fx) + L(j,i+1)*fx, bot likewise from row j+1,
+ *     v_o = (top*(c-fy) + bot*fy) >> 2s; S = sum (8 >> o) * v_o; S16 = (S * 4369) >> 16;
+ *     alpha = lo + (((hi - lo) * S16) >> 16); per channel out = (v*(65536 - alpha) + air*alpha + 32768) >> 16.
+ *   op 3 rain (integers): a drop head sits at (yy, xx) when, with X = xx + 4096 and
+ *     w = philox(X >> 2, yy, 0x5241494e, 0), (w[X & 3] & 0xffff) < thr (components x, y, z, w);
+ *     R = max over k in 0..len-1 of head(y + k, x + ((k*slant) >> 3)) * (256 - k*fade) (arithmetic shift);
+ *     out = v + (((255 - v) * beta * R) >> 16). Streaks enter from outside the image through the same hash.
+ * One descriptor per image, in a host array: */
+typedef struct mx_weather_desc {
+  const uint8_t* src; /* device, u8 [H][W][3] */
+  uint8_t* dst;       /* device, u8 [H][W][3]; may be src (every op reads only the pixel it writes) */
+  int32_t H, W;       /* 1..32768 each */
+  int32_t op;         /* 1 night, 2 haze, 3 rain */
+  float gain;         /* op 1: finite, >= 0 */
+  uint64_t seed;      /* the Philox key of every op */
+  float shot, read2;  /* op 1: finite, >= 0 */
+  int32_t lo, hi, air; /* op 2: q16 0 <= lo <= hi <= 65535; air 0..255 */
+  int32_t thr, len, slant, fade, beta; /* op 3: thr 0..65535, len 1..32, slant -8..8, fade >= 0 with
+                                          (len-1)*fade < 256, beta 0..256 */
+} mx_weather_desc;
+/* noise: NULL, or one f32 field on the device for the whole call, laid out as in mx_corrupt_batch_u8 (the
+ * images' [H][W][3] fields back to back in descriptor order, whatever their ops); only op 1 reads it.
+ * Every descriptor is checked before the first launch and a failure returns MX_EINVAL: null pointers, a
+ * bad op, a bad size, parameters out of range, src and dst ranges that overlap without being equal, an
+ * output that overlaps another image's input or output. */
+int mx_weather_batch_u8(const mx_weather_desc* descs_host, int64_t n, const float* noise, mx_stream_t stream);
+/* out[0], out[1] = rows, columns of the output tile one workgroup of mx_weather_batch_u8 owns. */
+int mx_weather_batch_tile(int32_t out[2]);
 /* GeneralizedRCNNTransform (normalize, zero-pad to /32) fused with ToDtype(scale=True):
  * u8 HWC [B,H,W,3] -> NHWC [B, Hp, Wp, Cp] dtype, (x/255 - mean)/std, zero padding; Cp >= 3 (extra
  * channels zero, for the conv stem's 8-channel gather). */

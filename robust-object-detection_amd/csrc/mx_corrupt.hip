@@ -15,7 +15,7 @@
 //     first builds OpenCV's (source, alpha) table of every staged column and row in LDS, once each, not
 //     once per pixel) -- then, after one barrier, the 11-bit up-scale runs out of LDS. No intermediate
 //     image in HBM, no second launch.
-// Stores. A wave owns a tile row at a time; lane g owns the g-th aligned dword of that row's byte span
+// Stores (cb_store_tile, mx_corrupt_tile.h, shared with mx_weather.hip). A wave owns a tile row at a time; lane g owns the g-th aligned dword of that row's byte span
 // (<= 61 dwords of 240 bytes plus misalignment), computes its 4 bytes and writes one dword; the first
 // and last dword of a row, where they are partial, are written byte by byte.
 #include <algorithm>
@@ -23,10 +23,10 @@
 
 #include "mx_common.h"
 #include "mx_corrupt_ops.h"
+#include "mx_corrupt_tile.h"
 
 namespace mx {
 
-static constexpr int CB_ROWS = 16, CB_COLS = 80, CB_THREADS = 256;
 static constexpr int CB_HALO = 15;                      // largest tap reach
 static constexpr int CB_IMGS = 16, CB_TAPS = 192;       // per chunk (kernel argument)
 static constexpr int CB_BLUR_COLS = CB_COLS + 2 * CB_HALO, CB_BLUR_ROWS = CB_ROWS + 2 * CB_HALO;
@@ -46,7 +46,6 @@ static constexpr int CB_LR_LDS = CB_LR_TABS + (CB_LR_COLS + CB_LR_ROWS) * (int)s
 static constexpr int CB_LDS = CB_BLUR_ROWS * CB_BLUR_STRIDE > CB_LR_LDS ? CB_BLUR_ROWS * CB_BLUR_STRIDE : CB_LR_LDS;
 static_assert(CB_LR_TABS % 4 == 0, "the tables are word-aligned");
 static_assert(CB_BLUR_STRIDE % 4 == 0 && CB_LR_STRIDE % 4 == 0, "LDS rows start on a bank boundary");
-static_assert((CB_COLS * 3 + 3 + 3) / 4 <= 64, "one lane per aligned dword of a tile row");
 
 struct CbImg {
   const uint8_t* src;
@@ -68,38 +67,6 @@ struct CbChunk {
   int32_t n;
 };
 static_assert(sizeof(CbChunk) <= 3072, "the chunk travels as a kernel argument");
-
-// The store side, shared by every op: val(r, e) is output byte e (x * 3 + c within the tile row) of tile
-// row r. Lane g of the wave that owns row r writes the aligned dword g of the row's span.
-template <typename Val>
-__device__ __forceinline__ void cb_store_tile(uint8_t* dst, int W, int y0, int x0, int rows, int cols, Val val) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int len = cols * 3;
-  for (int r = wave; r < rows; r += CB_THREADS / 64) {
-    uint8_t* rowp = dst + ((int64_t)(y0 + r) * W + x0) * 3;
-    const int mis = (int)((uintptr_t)rowp & 3);
-    const int start = lane * 4 - mis;  // first byte of this lane's dword, relative to the row
-    if (start >= len) continue;
-    // the four values are computed once, on one path for the whole wave (a row's partial first or last
-    // dword would otherwise send its wave through the arithmetic twice); a byte outside the row stands
-    // in for its nearest neighbour inside, which this lane owns, and is not stored
-    uint8_t v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int e = start + j;
-      v[j] = val(r, e < 0 ? 0 : (e >= len ? len - 1 : e));
-    }
-    if (start >= 0 && start + 4 <= len) {
-      *(uint32_t*)(rowp + start) = (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 | (uint32_t)v[3] << 24;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int e = start + j;
-        if (e >= 0 && e < len) rowp[e] = v[j];
-      }
-    }
-  }
-}
 
 __global__ void __launch_bounds__(CB_THREADS) corrupt_batch_kernel(CbChunk ck) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[CB_LDS];

@@ -43,6 +43,16 @@ class CorruptDesc(ctypes.Structure):
                 ("tap_off", ctypes.c_int32), ("ntaps", ctypes.c_int32), ("nh", ctypes.c_int32), ("nw", ctypes.c_int32)]
 
 
+class WeatherDesc(ctypes.Structure):
+    """mx_weather_desc (include/mx_det.h): one image of an mx_weather_batch_u8 call."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("op", ctypes.c_int32), ("gain", ctypes.c_float), ("seed", ctypes.c_uint64),
+                ("shot", ctypes.c_float), ("read2", ctypes.c_float),
+                ("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("air", ctypes.c_int32),
+                ("thr", ctypes.c_int32), ("len", ctypes.c_int32), ("slant", ctypes.c_int32),
+                ("fade", ctypes.c_int32), ("beta", ctypes.c_int32)]
+
+
 class JpegInfo(ctypes.Structure):
     """mx_jpeg_info (include/mx_det.h)."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32),
@@ -102,6 +112,8 @@ _SIGS = {
     "mx_filter2d_u8": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp]),
     "mx_corrupt_batch_u8": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "mx_corrupt_batch_tile": (c_int, [c_vp]),
+    "mx_weather_batch_u8": (c_int, [c_vp, c_i64, c_vp, c_vp]),
+    "mx_weather_batch_tile": (c_int, [c_vp]),
     "mx_normalize_pad": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp]),
     "mx_resize_normalize_pad": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_int,
                                         c_vp, c_vp]),

@@ -13,6 +13,9 @@ SEVERITY gives every corruption five levels (level 3 = the constants above); sev
 / severity_variants and the `severities` parameter of RandomCorruptionGPU put them to use through
 ops.corrupt_batch_u8 (one launch for a batch with its own kind and strength per image). Opt-in: with the
 default (3,) every call and every random draw is the one without it.
+Night, haze and rain (WEATHER_KINDS; this project's own definitions, include/mx_det.h) are three more
+opt-in kinds with five levels each: apply_night / apply_haze / apply_rain on numpy images, and the names
+in MX_CORRUPTIONS / MX_EXTRA_VARIANTS; they run through ops.weather_batch_u8 / ops.corrupt_batch_u8.
 """
 import random
 
@@ -29,7 +32,8 @@ JPEG_QUALITY = 15  # ImageNet-C's middle severity of its JPEG corruption; a cons
 JPEG_SUBSAMPLING = 2  # 4:2:0, PIL's default for that quality
 
 DEFAULT_KINDS = ("noise", "blur", "lowres")  # the reference's corruptions
-KINDS = DEFAULT_KINDS + ("jpeg",)
+WEATHER_KINDS = ("night", "haze", "rain")  # mx_weather_batch_u8's ops
+KINDS = DEFAULT_KINDS + ("jpeg",) + WEATHER_KINDS
 
 
 def check_kinds(kinds):
@@ -51,12 +55,13 @@ def env_kinds(value=None):
     return check_kinds(value)
 
 
-EXTRA_VARIANTS = {"jpeg": ("Test_JPEG", "JPEG")}  # name -> (test-set variant, its short name)
+EXTRA_VARIANTS = {"jpeg": ("Test_JPEG", "JPEG"), "night": ("Test_Night", "Night"), "haze": ("Test_Haze", "Haze"),
+                  "rain": ("Test_Rain", "Rain")}  # name -> (test-set variant, its short name)
 
 
 def env_extra_variants(value=None):
     """Test-set variants beyond the reference's four, as [(variant, short name)]: `value`, or
-    MX_EXTRA_VARIANTS, a comma-separated list (default empty; jpeg is the only name)."""
+    MX_EXTRA_VARIANTS, a comma-separated list (default empty; the names are jpeg, night, haze, rain)."""
     import os
     value = os.environ.get("MX_EXTRA_VARIANTS", "") if value is None else value
     names = [k.strip() for k in value.split(",") if k.strip()] if isinstance(value, str) else list(value)
@@ -67,8 +72,8 @@ def env_extra_variants(value=None):
 
 
 # Severity levels 1..5 of every corruption; constants of this project. Level 3 is the reference's
-# setting in every row (NOISE_SIGMA, BLUR_KERNEL, DOWNSCALE_FACTOR, JPEG_QUALITY); the JPEG row is
-# ImageNet-C's five qualities.
+# setting in every row it has one for (NOISE_SIGMA, BLUR_KERNEL, DOWNSCALE_FACTOR, JPEG_QUALITY); the JPEG row
+# is ImageNet-C's five qualities. Night, haze and rain are this project's own ops and rows.
 SEVERITY_LEVELS = (1, 2, 3, 4, 5)
 DEFAULT_SEVERITIES = (3,)
 SEVERITY = {
@@ -76,9 +81,14 @@ SEVERITY = {
     "blur": (5, 7, 9, 13, 17),                       # kernel size k, at BLUR_ANGLE_DEG
     "lowres": (0.75, 0.625, 0.5, 0.375, 0.25),       # down-scale factor
     "jpeg": (25, 18, 15, 10, 7),                     # quality
+    "night": ((0.6, 0.1, 2), (0.45, 0.15, 3), (0.3, 0.25, 4), (0.2, 0.4, 6), (0.12, 0.6, 8)),  # gain, shot, read
+    "haze": ((0.10, 0.35), (0.20, 0.50), (0.30, 0.65), (0.40, 0.78), (0.50, 0.90)),            # alpha lo, hi
+    "rain": ((131, 9, 110), (262, 13, 130), (393, 17, 150), (590, 23, 170), (786, 31, 190)),   # thr, len, beta
 }
+HAZE_AIR = 235    # the airlight every haze level blends towards
+RAIN_SLANT = 2    # columns per 8 rows of streak; fade = 256 // len
 KIND_VARIANTS = {"noise": ("Test_Noise", "Noise"), "blur": ("Test_Blur", "Blur"), "lowres": ("Test_LowRes", "LowRes"),
-                 "jpeg": EXTRA_VARIANTS["jpeg"]}  # kind -> (its level-3 test-set variant, short name)
+                 **EXTRA_VARIANTS}  # kind -> (its level-3 test-set variant, short name)
 
 
 def check_severities(levels):
@@ -106,7 +116,8 @@ def env_severities(value=None):
 
 
 def severity_value(kind, level):
-    """The strength of `kind` at `level`: sigma, kernel size, down-scale factor or JPEG quality."""
+    """The strength of `kind` at `level`: sigma, kernel size, down-scale factor or JPEG quality; the
+    SEVERITY row's tuple for night, haze and rain."""
     if kind not in SEVERITY or level not in SEVERITY_LEVELS:
         raise ValueError(f"no severity {level!r} of corruption {kind!r}")
     return SEVERITY[kind][level - 1]
@@ -130,6 +141,14 @@ def severity_spec(kind, level):
         return ops.CorruptSpec(ops.CORRUPT_BLUR, _blur_taps(v))
     if kind == "lowres":
         return ops.CorruptSpec(ops.CORRUPT_LOWRES, float(v))
+    if kind == "night":
+        gain, shot, read = v
+        return ops.CorruptSpec(ops.CORRUPT_NIGHT, (float(gain), float(shot), float(read * read)))
+    if kind == "haze":
+        return ops.CorruptSpec(ops.CORRUPT_HAZE, (round(v[0] * 65536), round(v[1] * 65536), HAZE_AIR))
+    if kind == "rain":
+        thr, length, beta = v
+        return ops.CorruptSpec(ops.CORRUPT_RAIN, (thr, length, RAIN_SLANT, 256 // length, beta))
     return ops.CorruptSpec(ops.CORRUPT_JPEG, int(v))
 
 
@@ -239,6 +258,30 @@ def apply_jpeg(img_bgr: np.ndarray, quality: int) -> np.ndarray:
     return ops.corrupt_jpeg_u8(t, int(quality), JPEG_SUBSAMPLING, bgr=True)[0].cpu().numpy()
 
 
+def _apply_weather(img_bgr, kind, level, seed):
+    t = torch.from_numpy(np.ascontiguousarray(img_bgr, dtype=np.uint8)).to(_dev())
+    seed = random.getrandbits(63) if seed is None else int(seed)
+    return ops.weather_batch_u8([t], [severity_spec(kind, level)], seed=seed)[0].cpu().numpy()
+
+
+def apply_night(img_bgr: np.ndarray, level: int = 3, seed=None) -> np.ndarray:
+    """Low light at SEVERITY["night"][level - 1]: the image dimmed by `gain`, plus signal-dependent
+    (shot) and constant (read) sensor noise from the device generator. seed None: random.getrandbits(63)."""
+    return _apply_weather(img_bgr, "night", level, seed)
+
+
+def apply_haze(img_bgr: np.ndarray, level: int = 3, seed=None) -> np.ndarray:
+    """Haze at SEVERITY["haze"][level - 1]: a blend towards HAZE_AIR by a smooth four-octave field
+    between the row's two alphas. seed None: random.getrandbits(63)."""
+    return _apply_weather(img_bgr, "haze", level, seed)
+
+
+def apply_rain(img_bgr: np.ndarray, level: int = 3, seed=None) -> np.ndarray:
+    """Rain at SEVERITY["rain"][level - 1]: slanted, fading streaks below hashed drop heads, lightening
+    the pixels they cover. seed None: random.getrandbits(63)."""
+    return _apply_weather(img_bgr, "rain", level, seed)
+
+
 def _apply_random_corruption(img_bgr: np.ndarray, kinds=DEFAULT_KINDS) -> np.ndarray:
     choice = _choice(kinds)
     if choice == "noise":
@@ -247,12 +290,14 @@ def _apply_random_corruption(img_bgr: np.ndarray, kinds=DEFAULT_KINDS) -> np.nda
         return apply_motion_blur(img_bgr, BLUR_KERNEL, BLUR_ANGLE_DEG)
     if choice == "jpeg":
         return apply_jpeg(img_bgr, JPEG_QUALITY)
+    if choice in WEATHER_KINDS:
+        return {"night": apply_night, "haze": apply_haze, "rain": apply_rain}[choice](img_bgr)
     return apply_lowres(img_bgr, DOWNSCALE_FACTOR)
 
 
 class RandomCorruption:
     """PIL transform: with probability p apply one random corruption (augmentations.py:60-74), drawn
-    from `kinds` (the reference's three by default; "jpeg" may join them)."""
+    from `kinds` (the reference's three by default; "jpeg", "night", "haze" and "rain" may join them)."""
 
     def __init__(self, p: float = 0.5, kinds=DEFAULT_KINDS):
         self.p = p
@@ -274,10 +319,12 @@ class RandomCorruptionGPU:
     severities: the levels a corrupted image draws from, random.choice(severities) after its kind. The
     default (3,) draws nothing more and makes exactly the calls the class made before the parameter;
     anything else goes through ops.corrupt_batch_u8, and batch(imgs) corrupts a list of frames of any
-    sizes in one call."""
+    sizes in one call. A "night", "haze" or "rain" draw goes through ops.corrupt_batch_u8 at any severities
+    (level 3, without a level draw, at the default ones)."""
 
     CODES = {"noise": ops.CORRUPT_NOISE, "blur": ops.CORRUPT_BLUR, "lowres": ops.CORRUPT_LOWRES,
-             "jpeg": ops.CORRUPT_JPEG}
+             "jpeg": ops.CORRUPT_JPEG, "night": ops.CORRUPT_NIGHT, "haze": ops.CORRUPT_HAZE,
+             "rain": ops.CORRUPT_RAIN}
 
     def __init__(self, p: float = 0.5, kinds=DEFAULT_KINDS, severities=DEFAULT_SEVERITIES):
         self.p = p
@@ -288,10 +335,11 @@ class RandomCorruptionGPU:
         if random.random() > self.p:
             return img
         kind = _choice(self.kinds)
-        if self.severities == DEFAULT_SEVERITIES:
+        if self.severities == DEFAULT_SEVERITIES and kind not in WEATHER_KINDS:
             return ops.corrupt_u8(img[None], [self.CODES[kind]], sigma=NOISE_SIGMA, seed=random.getrandbits(63),
                                   factor=DOWNSCALE_FACTOR, quality=JPEG_QUALITY, subsampling=JPEG_SUBSAMPLING)[0]
-        spec = severity_spec(kind, random.choice(self.severities))
+        level = 3 if self.severities == DEFAULT_SEVERITIES else random.choice(self.severities)
+        spec = severity_spec(kind, level)
         return ops.corrupt_batch_u8([img], [spec], seed=random.getrandbits(63), subsampling=JPEG_SUBSAMPLING)[0]
 
     def batch(self, imgs):

@@ -646,6 +646,10 @@ def detections_postprocess(logits, reg, rois, img, hw, N, score_thresh, nms_thre
 # ---------------------------------------------------------------------------------------------
 CORRUPT_NONE, CORRUPT_NOISE, CORRUPT_BLUR, CORRUPT_LOWRES = 0, 1, 2, 3
 CORRUPT_JPEG = 4  # not an mx_corrupt_u8 op: corrupt_u8 hands these images to mx_corrupt_jpeg_u8
+# not mx_corrupt_u8 / mx_corrupt_batch_u8 ops: weather_batch_u8 and corrupt_batch_u8 hand these images to
+# mx_weather_batch_u8 (its ops 1, 2, 3)
+CORRUPT_NIGHT, CORRUPT_HAZE, CORRUPT_RAIN = 5, 6, 7
+_WEATHER = (CORRUPT_NIGHT, CORRUPT_HAZE, CORRUPT_RAIN)
 
 
 def corrupt_jpeg_u8(images, quality, subsampling=2, bgr=False, out=None):
@@ -718,7 +722,8 @@ def filter2d_u8(images, taps):
 
 CorruptSpec = collections.namedtuple("CorruptSpec", ("op", "param"), defaults=(None,))
 CorruptSpec.__doc__ = """One image's corruption in corrupt_batch_u8: (CORRUPT_NONE,), (CORRUPT_NOISE, sigma),
-(CORRUPT_BLUR, taps as (dy, dx, coef) rows), (CORRUPT_LOWRES, factor), (CORRUPT_JPEG, quality)."""
+(CORRUPT_BLUR, taps as (dy, dx, coef) rows), (CORRUPT_LOWRES, factor), (CORRUPT_JPEG, quality),
+(CORRUPT_NIGHT, (gain, shot, read2)), (CORRUPT_HAZE, (lo, hi, air)), (CORRUPT_RAIN, (thr, len, slant, fade, beta))."""
 
 _SEED_STEP = 0x9E3779B97F4A7C15  # image b's Philox seed is seed + _SEED_STEP * b (mx_corrupt_u8's rule)
 
@@ -730,17 +735,18 @@ def corrupt_batch_tile():
     return int(rc[0]), int(rc[1])
 
 
-def corrupt_batch_u8(images, specs, seed=0, noise=None, out=None, subsampling=2, bgr=False):
-    """The corruptions with one (kind, strength) per image, the whole batch in one device launch
-    (mx_corrupt_batch_u8; chunks of 16 images): images is uint8 [B,H,W,3] or a list of uint8 [H,W,3]
-    tensors of any sizes, specs one CorruptSpec (or plain tuple) per image. Each image gets the bits
-    corrupt_u8 / filter2d_u8 / corrupt_jpeg_u8 give for it alone: noise from Philox with image b's seed
-    seed + 0x9E3779B97F4A7C15 * b (or from `noise`: f32 like images, or a list of per-image fields),
-    low-res at nh, nw = max(1, int(H * factor)), max(1, int(W * factor)). CORRUPT_JPEG images are
-    copied by the launch and then compressed by corrupt_jpeg_u8 (`subsampling`, `bgr`), one call per
-    image size. out: a tensor / list like images to write into; an entry that is its own image runs in
-    place (noise and identity only). Returns a tensor for a tensor, a list for a list."""
+def weather_batch_tile():
+    """(rows, columns) of the output tile one workgroup of mx_weather_batch_u8 owns."""
+    rc = (ctypes.c_int32 * 2)()
+    call("mx_weather_batch_tile", rc)
+    return int(rc[0]), int(rc[1])
+
+
+def _batch_io(images, out, name):
+    """The images and outputs of a batched corruption call: (batched, x, xs, out, outs) for uint8
+    [B,H,W,3] or a list of uint8 [H,W,3] tensors; out as given, or new tensors like the images."""
     batched = torch.is_tensor(images)
+    x = None
     if batched:
         _dev(images)
         _check(images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3, "images must be uint8 [B,H,W,3]")
@@ -752,8 +758,6 @@ def corrupt_batch_u8(images, specs, seed=0, noise=None, out=None, subsampling=2,
             _dev(im)
             _check(im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3, "images must be uint8 [H,W,3]")
     B = len(xs)
-    specs = [CorruptSpec(*s) for s in specs]
-    _check(len(specs) == B, "corrupt_batch_u8: one spec per image")
     if out is None:
         if batched:
             out = torch.empty_like(x)
@@ -763,26 +767,106 @@ def corrupt_batch_u8(images, specs, seed=0, noise=None, out=None, subsampling=2,
     else:
         if batched:
             _check(torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == x.device and out.shape == x.shape
-                   and out.is_contiguous(), "corrupt_batch_u8: out must be a contiguous uint8 tensor like images")
+                   and out.is_contiguous(), f"{name}: out must be a contiguous uint8 tensor like images")
             outs = list(out.unbind(0))
         else:
             outs = list(out)
             _check(len(outs) == B and all(torch.is_tensor(o) and o.dtype == torch.uint8 and o.shape == im.shape
                                           and o.device == im.device and o.is_contiguous() for o, im in zip(outs, xs)),
-                   "corrupt_batch_u8: out must list one contiguous uint8 tensor like each image")
+                   f"{name}: out must list one contiguous uint8 tensor like each image")
+    return batched, x, xs, out, outs
+
+
+def _batch_noise(noise, xs):
+    """The call's noise field as one flat f32 device tensor (None stays None)."""
+    if noise is None:
+        return None
+    if torch.is_tensor(noise):
+        noise = noise.float().contiguous()
+    else:
+        noise = torch.cat([n.float().reshape(-1) for n in noise])
+    _dev(noise)
+    _check(noise.numel() == sum(im.numel() for im in xs), "noise field must match images")
+    return noise
+
+
+def _weather_call(xs, outs, specs, seeds, noise):
+    """One mx_weather_batch_u8 call: image k under specs[k] with the Philox seed seeds[k]; noise: None or
+    the f32 fields of exactly these images, back to back."""
+    n = len(xs)
+    descs = (_lib.WeatherDesc * n)()
+    for d, im, o, sp, sd in zip(descs, xs, outs, specs, seeds):
+        d.src, d.dst, d.H, d.W = im.data_ptr(), o.data_ptr(), int(im.shape[0]), int(im.shape[1])
+        op = int(sp.op)
+        d.op = op - CORRUPT_JPEG  # mx_weather_batch_u8: 1 night, 2 haze, 3 rain
+        d.seed = int(sd) & (2 ** 64 - 1)
+        if op == CORRUPT_NIGHT:
+            _check(len(sp.param) == 3, "night takes (gain, shot, read2)")
+            d.gain, d.shot, d.read2 = (float(v) for v in sp.param)
+        elif op == CORRUPT_HAZE:
+            _check(len(sp.param) == 3, "haze takes (lo, hi, air)")
+            d.lo, d.hi, d.air = (int(v) for v in sp.param)
+        else:
+            _check(len(sp.param) == 5, "rain takes (thr, len, slant, fade, beta)")
+            d.thr, d.len, d.slant, d.fade, d.beta = (int(v) for v in sp.param)
+    call("mx_weather_batch_u8", descs, n, _p(noise), _stream())
+
+
+def weather_batch_u8(images, specs, seed=0, noise=None, out=None):
+    """Night, haze and rain with one (kind, parameters) per image, the whole batch in one device launch
+    (mx_weather_batch_u8; chunks of 16 images): images is uint8 [B,H,W,3] or a list of uint8 [H,W,3]
+    tensors of any sizes, specs one CorruptSpec (or plain tuple) per image: (CORRUPT_NIGHT, (gain, shot,
+    read2)), (CORRUPT_HAZE, (lo, hi, air)) with lo, hi in q16, (CORRUPT_RAIN, (thr, len, slant, fade,
+    beta)); include/mx_det.h defines the three ops. Image b's Philox seed is seed + 0x9E3779B97F4A7C15 * b.
+    noise: night's normal field instead of the device generator, f32 like images or a list of per-image
+    fields. out: a tensor / list like images to write into; an entry may be its own image (every op runs in
+    place). Returns a tensor for a tensor, a list for a list."""
+    batched, x, xs, out, outs = _batch_io(images, out, "weather_batch_u8")
+    specs = [CorruptSpec(*s) for s in specs]
+    _check(len(specs) == len(xs), "weather_batch_u8: one spec per image")
+    _check(all(int(sp.op) in _WEATHER for sp in specs), "weather_batch_u8: specs must be night, haze or rain")
+    if xs:
+        noise = _batch_noise(noise, xs)
+        _weather_call(xs, outs, specs, [int(seed) + _SEED_STEP * b for b in range(len(xs))], noise)
+    return out if batched else outs
+
+
+def corrupt_batch_u8(images, specs, seed=0, noise=None, out=None, subsampling=2, bgr=False):
+    """The corruptions with one (kind, strength) per image, the whole batch in one device launch
+    (mx_corrupt_batch_u8; chunks of 16 images): images is uint8 [B,H,W,3] or a list of uint8 [H,W,3]
+    tensors of any sizes, specs one CorruptSpec (or plain tuple) per image. Each image gets the bits
+    corrupt_u8 / filter2d_u8 / corrupt_jpeg_u8 give for it alone: noise from Philox with image b's seed
+    seed + 0x9E3779B97F4A7C15 * b (or from `noise`: f32 like images, or a list of per-image fields),
+    low-res at nh, nw = max(1, int(H * factor)), max(1, int(W * factor)). CORRUPT_JPEG images are
+    copied by the launch and then compressed by corrupt_jpeg_u8 (`subsampling`, `bgr`), one call per
+    image size. CORRUPT_NIGHT / CORRUPT_HAZE / CORRUPT_RAIN images are left out of that launch and run
+    in one mx_weather_batch_u8 call (the bits weather_batch_u8 gives image b alone under seed +
+    0x9E3779B97F4A7C15 * b); a batch without them makes the calls it made before they existed. out: a
+    tensor / list like images to write into; an entry that is its own image runs in place (noise,
+    identity and the three weather kinds only). Returns a tensor for a tensor, a list for a list."""
+    batched, x, xs, out, outs = _batch_io(images, out, "corrupt_batch_u8")
+    B = len(xs)
+    specs = [CorruptSpec(*s) for s in specs]
+    _check(len(specs) == B, "corrupt_batch_u8: one spec per image")
     if B == 0:
         return out if batched else outs
-    if noise is not None:
-        if torch.is_tensor(noise):
-            noise = noise.float().contiguous()
-        else:
-            noise = torch.cat([n.float().reshape(-1) for n in noise])
-        _dev(noise)
-        _check(noise.numel() == sum(im.numel() for im in xs), "noise field must match images")
-    descs = (_lib.CorruptDesc * B)()
+    noise = _batch_noise(noise, xs)
+    wx = [b for b, sp in enumerate(specs) if int(sp.op) in _WEATHER]
+    rest = list(range(B))
+    wx_noise = None
+    if wx:
+        rest = [b for b in rest if int(specs[b].op) not in _WEATHER]
+        if noise is not None:  # each call takes the fields of its own images, back to back
+            offs = [0]
+            for im in xs:
+                offs.append(offs[-1] + im.numel())
+            flat = noise.reshape(-1)
+            wx_noise = torch.cat([flat[offs[b]:offs[b + 1]] for b in wx])
+            noise = torch.cat([flat[offs[b]:offs[b + 1]] for b in rest]) if rest else None
+    descs = (_lib.CorruptDesc * max(len(rest), 1))()
     taps, tap_sets, jpeg = [], {}, {}
-    for b, (im, o, sp) in enumerate(zip(xs, outs, specs)):
-        d = descs[b]
+    for d, b in zip(descs, rest):
+        im, o, sp = xs[b], outs[b], specs[b]
         H, W = int(im.shape[0]), int(im.shape[1])
         d.src, d.dst, d.H, d.W = im.data_ptr(), o.data_ptr(), H, W
         op = int(sp.op)
@@ -801,9 +885,13 @@ def corrupt_batch_u8(images, specs, seed=0, noise=None, out=None, subsampling=2,
         elif op == CORRUPT_JPEG:
             _check(1 <= int(sp.param) <= 100, "corrupt_batch_u8: quality must be 1..100")
             jpeg.setdefault((H, W), []).append(b)
-    call("mx_corrupt_batch_u8", descs, B, (ctypes.c_float * max(len(taps), 1))(*taps), len(taps) // 3, _p(noise),
-         _stream())
-    if jpeg and batched:  # one size: the rows with quality 0 keep what the launch wrote
+    if rest:
+        call("mx_corrupt_batch_u8", descs, len(rest), (ctypes.c_float * max(len(taps), 1))(*taps), len(taps) // 3,
+             _p(noise), _stream())
+    if wx:
+        _weather_call([xs[b] for b in wx], [outs[b] for b in wx], [specs[b] for b in wx],
+                      [int(seed) + _SEED_STEP * b for b in wx], wx_noise)
+    if jpeg and batched:  # one size: the rows with quality 0 keep what the launches wrote
         corrupt_jpeg_u8(x, [int(sp.param) if int(sp.op) == CORRUPT_JPEG else 0 for sp in specs], subsampling, bgr, out=out)
     elif jpeg:
         for idx in jpeg.values():

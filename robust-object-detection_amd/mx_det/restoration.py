@@ -356,7 +356,8 @@ class DevicePatchLoader:
 class RestorationBatcher:
     """uint8 clean patches [B,S,S,3] (host) -> (corrupted, clean) f32 NCHW in [0, 1] on the device;
     each patch gets random.choice(noise, blur, lowres) as in _apply_random_corruption (:92-100), or a
-    uniform choice of `kinds` when those are given ("jpeg": compression at augment.JPEG_QUALITY).
+    uniform choice of `kinds` when those are given ("jpeg": compression at augment.JPEG_QUALITY; "night",
+    "haze", "rain": level 3 of their augment.SEVERITY rows, the batch then one ops.corrupt_batch_u8 call).
     severities other than the default (3,): each patch also draws random.choice(severities) after its
     kind, and the batch is one ops.corrupt_batch_u8 call (augment.SEVERITY: blind-severity training)."""
 
@@ -378,8 +379,13 @@ class RestorationBatcher:
                 codes = [random.choice((NOISE, BLUR, LOWRES)) for _ in range(x.shape[0])]
             else:
                 codes = [augment.RandomCorruptionGPU.CODES[random.choice(list(self.kinds))] for _ in range(x.shape[0])]
-            cor = ops.corrupt_u8(x, codes, seed=random.getrandbits(62), quality=augment.JPEG_QUALITY,
-                                 subsampling=augment.JPEG_SUBSAMPLING)
+            if set(self.kinds) & set(augment.WEATHER_KINDS):  # not mx_corrupt_u8 ops: the batched entry, at level 3
+                names = {c: k for k, c in augment.RandomCorruptionGPU.CODES.items()}
+                cor = ops.corrupt_batch_u8(x, [augment.severity_spec(names[c], 3) for c in codes],
+                                           seed=random.getrandbits(62), subsampling=augment.JPEG_SUBSAMPLING)
+            else:
+                cor = ops.corrupt_u8(x, codes, seed=random.getrandbits(62), quality=augment.JPEG_QUALITY,
+                                     subsampling=augment.JPEG_SUBSAMPLING)
         to = lambda t: t.permute(0, 3, 1, 2).float().div_(255.0)  # noqa: E731
         return to(cor), to(x)
 

@@ -21,6 +21,10 @@ MX_SEVERITIES (levels 1..5, default 3) appends, after all of those, Test_<Kind>_
 variant built and every level L other than 3 (augment.SEVERITY; level 3 is the plain Test_<Kind>), each
 image through ops.corrupt_batch_u8. Their noise fields continue the one np.random stream, so the sets
 above keep their bytes.
+MX_EXTRA_VARIANTS also takes night, haze and rain (Test_Night, Test_Haze, Test_Rain: level 3 of their
+augment.SEVERITY rows through ops.corrupt_batch_u8, and Test_<Kind>_s<L> under MX_SEVERITIES). They draw
+nothing from np.random: an image's Philox seed is weather_seed(its index in the sorted listing of its
+directory), so a rebuilt set is identical and the sets above keep their bytes.
 """
 import os
 import shutil
@@ -50,10 +54,19 @@ def variants():
     return VARIANTS + [v for v, _ in augment.env_extra_variants()] + [v[0] for v in augment.severity_variants()]
 
 
-def corrupt_severity(img_bgr, kind, level):
+def weather_seed(index):
+    """The Philox seed of image `index` (in the sorted listing of its directory) in the night, haze and
+    rain sets: fixed by SEED, whatever the order the images are built in."""
+    return (SEED << 32) + int(index)
+
+
+def corrupt_severity(img_bgr, kind, level, index=0):
     """`kind` at severity `level` on a BGR uint8 device tensor [H, W, 3] (ops.corrupt_batch_u8); noise
-    takes the next field of the np.random stream, like Test_Noise."""
+    takes the next field of the np.random stream, like Test_Noise; night, haze and rain take
+    weather_seed(index)."""
     noise = None
+    if kind in augment.WEATHER_KINDS:
+        return ops.corrupt_batch_u8(img_bgr[None], [augment.severity_spec(kind, level)], seed=weather_seed(index))[0]
     if kind == "noise":
         noise = np.random.normal(0, augment.severity_value(kind, level), tuple(img_bgr.shape)).astype(np.float32)
         noise = torch.from_numpy(noise).to(img_bgr.device)[None]
@@ -68,16 +81,18 @@ def ensure_dir(p):
     Path(p).mkdir(parents=True, exist_ok=True)
 
 
-def corrupt(img_bgr, variant):
+def corrupt(img_bgr, variant, index=0):
     """One variant of build_corrupted_testsets.py:140-150 on a BGR uint8 image, a device tensor
-    [H, W, 3] (returned on the device) or a numpy array (returned as numpy)."""
+    [H, W, 3] (returned on the device) or a numpy array (returned as numpy). index: the image's place in
+    the sorted listing of its directory (the night, haze and rain sets seed by it)."""
     sev = {v[0]: v[2:] for v in augment.severity_variants()}
+    sev.update({augment.KIND_VARIANTS[k][0]: (k, 3) for k in augment.WEATHER_KINDS})
     if variant in sev:
         if torch.is_tensor(img_bgr):
-            return corrupt_severity(img_bgr, *sev[variant])
+            return corrupt_severity(img_bgr, *sev[variant], index)
         dev = torch.device("cuda", torch.cuda.current_device())
         t = torch.from_numpy(np.ascontiguousarray(img_bgr, dtype=np.uint8)).to(dev)
-        return corrupt_severity(t, *sev[variant]).cpu().numpy()
+        return corrupt_severity(t, *sev[variant], index).cpu().numpy()
     if not torch.is_tensor(img_bgr):
         if variant == "Test_Noise":
             return augment.apply_noise(img_bgr, NOISE_SIGMA)
@@ -131,11 +146,13 @@ def _write_bgr(path, img_bgr):
 
 
 def _build_images(src_img_dir, dst_img_dir, variant):
-    for img_path in src_img_dir.glob("*.*"):
+    paths = list(src_img_dir.glob("*.*"))
+    index = {n: i for i, n in enumerate(sorted(p.name for p in paths))}
+    for img_path in paths:
         img = _read_bgr(img_path)
         if img is None:
             continue
-        _write_bgr(dst_img_dir / img_path.name, corrupt(img, variant))
+        _write_bgr(dst_img_dir / img_path.name, corrupt(img, variant, index[img_path.name]))
 
 
 def write_yolo_valonly_yaml(dst_root):

@@ -5,7 +5,8 @@ FRCNN branch of the reference's eval_all.py (:79-156, :198-213) on MI355X; the U
 YOLO branches are outside this build's scope and are reported as skipped.
 Outputs keep the reference schema: experiments/eval_results.json ({model: {variant: {mAP50_95, mAP50,
 per_class_ap50}}}) and experiments/eval_results.csv. torchrun shards the images per rank.
-MX_EXTRA_VARIANTS=jpeg adds the Test_JPEG set (column JPEG) after the reference's four; MX_SEVERITIES
+MX_EXTRA_VARIANTS=jpeg adds the Test_JPEG set (column JPEG) after the reference's four, and night / haze /
+rain the Test_Night / Test_Haze / Test_Rain sets (columns Night, Haze, Rain); MX_SEVERITIES
 (levels 1..5, default 3) adds the Test_<Kind>_s<L> sets after those (columns Noise-s1 and so on).
 """
 import csv

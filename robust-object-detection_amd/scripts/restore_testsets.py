@@ -6,7 +6,8 @@ do the JPEG decode (mx_det.jpeg.read_file; PIL for the files it does not handle)
 encode (mx_det.jpeg.write_file), both bit-identical to libjpeg-turbo: pixels never visit the host.
 MX_JPEG_ENCODE=host encodes with PIL instead; MX_JPEG_DECODE=device decodes the scan on the device
 too (the default decodes it on the host). The fused eval path (eval_restored.py) skips this step.
-MX_EXTRA_VARIANTS=jpeg restores Test_JPEG as well, MX_SEVERITIES the Test_<Kind>_s<L> sets.
+MX_EXTRA_VARIANTS=jpeg restores Test_JPEG as well (night, haze, rain: Test_Night, Test_Haze, Test_Rain),
+MX_SEVERITIES the Test_<Kind>_s<L> sets.
 """
 import os
 import shutil

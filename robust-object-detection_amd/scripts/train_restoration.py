@@ -13,7 +13,8 @@ frame in the training thread. MX_PATCH_LOADER=device decodes them on the device 
 (mx_det.restoration.DevicePatchLoader: only the crop is reconstructed; MX_JPEG_DECODE picks where the
 entropy decode runs); for a given seed its patch sequence differs from the host loader's.
 MX_CORRUPTIONS (comma-separated; default noise,blur,lowres, the reference's) names the corruptions the
-patches draw from; jpeg adds compression at augment.JPEG_QUALITY. MX_SEVERITIES (levels 1..5, default
+patches draw from; jpeg adds compression at augment.JPEG_QUALITY, night / haze / rain low light, haze
+and rain (level 3 of their augment.SEVERITY rows unless MX_SEVERITIES says otherwise). MX_SEVERITIES (levels 1..5, default
 3) names the severity levels each patch draws from (augment.SEVERITY; blind-severity training).
 """
 import json
