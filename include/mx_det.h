@@ -326,6 +326,42 @@ typedef struct mx_weather_desc {
 int mx_weather_batch_u8(const mx_weather_desc* descs_host, int64_t n, const float* noise, mx_stream_t stream);
 /* out[0], out[1] = rows, columns of the output tile one workgroup of mx_weather_batch_u8 owns. */
 int mx_weather_batch_tile(int32_t out[2]);
+/* Degradation statistics of a whole batch in one launch (csrc/mx_gate.hip), and a verdict per image from a
+ * rule list over them: the blind gate in front of the restoration U-Net. The launch scheme of
+ * mx_corrupt_batch_u8 (one workgroup per tile of one image, descriptors and rules as the kernel argument in
+ * chunks of 16 images: no workspace, no upload, no host synchronisation, no allocation, capturable in a
+ * graph); images of one call may differ in size. One memset of stats, then one launch per chunk.
+ *   Luma Y = (77 R + 150 G + 29 B + 128) >> 8. The sums run over the interior pixels, rows 1..H-2 and
+ *   columns 1..W-2 (no border rule), c the centre, Y(dy, dx) its neighbours, all exact int64:
+ *     stats[b] = { N, IMM, DX2, DY2, DXX2, DYY2, G2, H2 }
+ *     N    = (H-2)(W-2)
+ *     IMM  = sum |Y(-1,-1) + Y(-1,1) + Y(1,-1) + Y(1,1) - 2 (Y(-1,0) + Y(1,0) + Y(0,-1) + Y(0,1)) + 4 c|
+ *     DX2  = sum (Y(0,1) - Y(0,-1))^2            DY2  = sum (Y(1,0) - Y(-1,0))^2
+ *     DXX2 = sum (Y(0,1) - 2 c + Y(0,-1))^2      DYY2 = sum (Y(1,0) - 2 c + Y(-1,0))^2
+ *     G2   = DX2 + DY2                           H2   = DXX2 + DYY2
+ *   |IMM term| <= 2040 and |DXX term| <= 510, so with H * W <= 2^24 every sum is below 2^47 and, with rule
+ *   coefficients <= 65535, every product of a rule below 2^63.
+ *   Rule r fires when a * stats[b][i] > b * stats[b][j]; the first rule that fires gives verdict[b], else
+ *   default_verdict. 1 = restore, 0 = pass through. The verdict is evaluated on the device by the image's
+ *   last-arriving workgroup (integer sums: independent of arrival order; a second call into the same
+ *   buffers gives the same answer). */
+typedef struct mx_gate_desc {
+  const uint8_t* src; /* device, u8 [H][W][3] */
+  int32_t H, W;       /* >= 3 each, H * W <= 2^24 */
+  int32_t bgr;        /* 0: channel 0 is R; else channel 0 is B */
+} mx_gate_desc;
+typedef struct mx_gate_rule {
+  int32_t i, j;    /* 0..7: the sums compared */
+  int32_t a, b;    /* 0..65535 */
+  int32_t verdict; /* 0 or 1 */
+} mx_gate_rule;
+/* stats: device int64 [n][8]; verdict: device int32 [n]. Refused before any launch (MX_EINVAL, with a
+ * message): null pointers when n > 0, H < 3 or W < 3, H * W > 2^24, a rule out of bounds, nrules > 8, a
+ * verdict that is not 0 or 1. n == 0 launches nothing. */
+int mx_degradation_stats_u8(const mx_gate_desc* descs_host, int64_t n, const mx_gate_rule* rules_host, int32_t nrules,
+                            int32_t default_verdict, int64_t* stats, int32_t* verdict, mx_stream_t stream);
+/* out[0], out[1] = rows, columns of the tile of interior pixels one workgroup of mx_degradation_stats_u8 owns. */
+int mx_degradation_stats_tile(int32_t out[2]);
 /* GeneralizedRCNNTransform (normalize, zero-pad to /32) fused with ToDtype(scale=True):
  * u8 HWC [B,H,W,3] -> NHWC [B, Hp, Wp, Cp] dtype, (x/255 - mean)/std, zero padding; Cp >= 3 (extra
  * channels zero, for the conv stem's 8-channel gather). */
@@ -719,6 +755,11 @@ int mx_up_concat_bwd(const void* gcat, int dtype, int64_t N, int64_t H, int64_t 
                      void* gskip, mx_stream_t stream);
 int mx_restore_finish(const uint8_t* img_padded, int64_t B, int64_t Hp, int64_t Wp, const float* residual, int64_t H,
                       int64_t W, uint8_t* out, mx_stream_t stream);
+/* mx_restore_finish under a per-image verdict (device int32 [B], as mx_degradation_stats_u8 writes it; csrc/
+ * mx_gate.hip): for verdict[b] == 1 the bytes of mx_restore_finish, for 0 out[b] is the unpadded crop of
+ * img_padded[b] (the image passes through). */
+int mx_restore_finish_gated(const uint8_t* img_padded, int64_t B, int64_t Hp, int64_t Wp, const float* residual, int64_t H,
+                            int64_t W, const int32_t* verdict, uint8_t* out, mx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * U-Net training loss L1 + weight * (1 - SSIM) (train_restoration.py:142-178: ssim() with an 11x11

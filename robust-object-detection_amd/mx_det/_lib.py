@@ -53,6 +53,17 @@ class WeatherDesc(ctypes.Structure):
                 ("fade", ctypes.c_int32), ("beta", ctypes.c_int32)]
 
 
+class GateDesc(ctypes.Structure):
+    """mx_gate_desc (include/mx_det.h): one image of an mx_degradation_stats_u8 call."""
+    _fields_ = [("src", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("bgr", ctypes.c_int32)]
+
+
+class GateRule(ctypes.Structure):
+    """mx_gate_rule (include/mx_det.h): fires when a * stats[i] > b * stats[j]."""
+    _fields_ = [("i", ctypes.c_int32), ("j", ctypes.c_int32), ("a", ctypes.c_int32), ("b", ctypes.c_int32),
+                ("verdict", ctypes.c_int32)]
+
+
 class JpegInfo(ctypes.Structure):
     """mx_jpeg_info (include/mx_det.h)."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32),
@@ -114,6 +125,9 @@ _SIGS = {
     "mx_corrupt_batch_tile": (c_int, [c_vp]),
     "mx_weather_batch_u8": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "mx_weather_batch_tile": (c_int, [c_vp]),
+    "mx_degradation_stats_u8": (c_int, [c_vp, c_i64, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp]),
+    "mx_degradation_stats_tile": (c_int, [c_vp]),
+    "mx_restore_finish_gated": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "mx_normalize_pad": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp]),
     "mx_resize_normalize_pad": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_int,
                                         c_vp, c_vp]),

@@ -901,6 +901,59 @@ def corrupt_batch_u8(images, specs, seed=0, noise=None, out=None, subsampling=2,
     return out if batched else outs
 
 
+def degradation_stats_tile():
+    """(rows, columns) of the tile of interior pixels one workgroup of mx_degradation_stats_u8 owns."""
+    rc = (ctypes.c_int32 * 2)()
+    call("mx_degradation_stats_tile", rc)
+    return int(rc[0]), int(rc[1])
+
+
+def degradation_stats_u8(images, rules=None, default=0, bgr=False, out=None):
+    """The eight degradation sums of every image and the verdict of a rule list over them, the whole batch
+    in one device launch (mx_degradation_stats_u8; chunks of 16 images), with no host synchronisation:
+    images is uint8 [B,H,W,3] or a list of uint8 [H,W,3] tensors of any sizes (H, W >= 3, H * W <= 2^24).
+    rules: mx_det.gate.Rule tuples (i, j, a, b, verdict), at most 8, the first with a * stats[i] >
+    b * stats[j] gives the verdict, else `default`; None: gate.DEFAULT_RULES. Returns (stats int64 [B,8] =
+    N, IMM, DX2, DY2, DXX2, DYY2, G2, H2 as include/mx_det.h defines them, verdict int32 [B]; 1 = restore).
+    out: a (stats, verdict) pair of such tensors to write into."""
+    from . import gate
+    rules = gate.DEFAULT_RULES if rules is None else rules
+    if torch.is_tensor(images):
+        _dev(images)
+        _check(images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3, "images must be uint8 [B,H,W,3]")
+        xs = list(images.contiguous().unbind(0))
+        device = images.device
+    else:
+        xs = [im.contiguous() for im in images]
+        for im in xs:
+            _dev(im)
+            _check(im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3, "images must be uint8 [H,W,3]")
+        _check(all(im.device == xs[0].device for im in xs), "degradation_stats_u8: images on one device")
+        device = xs[0].device if xs else (out[0].device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+    B = len(xs)
+    if out is None:
+        stats = torch.empty((B, 8), dtype=torch.int64, device=device)
+        verdict = torch.empty((B,), dtype=torch.int32, device=device)
+    else:
+        stats, verdict = out
+        _check(torch.is_tensor(stats) and stats.dtype == torch.int64 and tuple(stats.shape) == (B, 8) and stats.is_contiguous()
+               and stats.device == device, "degradation_stats_u8: out[0] must be a contiguous int64 [B,8] tensor on the images' device")
+        _check(torch.is_tensor(verdict) and verdict.dtype == torch.int32 and tuple(verdict.shape) == (B,)
+               and verdict.is_contiguous() and verdict.device == device,
+               "degradation_stats_u8: out[1] must be a contiguous int32 [B] tensor on the images' device")
+    rules = [gate.Rule(*r) for r in rules]
+    rarr = (_lib.GateRule * max(len(rules), 1))()
+    for d, r in zip(rarr, rules):
+        d.i, d.j, d.a, d.b, d.verdict = int(r.i), int(r.j), int(r.a), int(r.b), int(r.verdict)
+    descs = (_lib.GateDesc * max(B, 1))()
+    for d, im in zip(descs, xs):
+        d.src, d.H, d.W, d.bgr = im.data_ptr(), int(im.shape[0]), int(im.shape[1]), int(bool(bgr))
+    # the library checks sizes, rules and the default before it launches anything
+    call("mx_degradation_stats_u8", descs, B, rarr, len(rules), int(default), _p(stats) if B else None,
+         _p(verdict) if B else None, _stream())
+    return stats, verdict
+
+
 IMAGE_MEAN = (0.485, 0.456, 0.406)
 IMAGE_STD = (0.229, 0.224, 0.225)
 

@@ -208,8 +208,10 @@ class RestorationUNet(nn.Module):
         return torch.clamp(x + r.permute(0, 3, 1, 2), 0.0, 1.0)
 
     @torch.no_grad()
-    def restore_u8(self, img_u8):
-        """restore_testsets.py:53-79 on device. img_u8 [B,H,W,3] uint8 (RGB) -> restored uint8 [B,H,W,3]."""
+    def restore_u8(self, img_u8, verdict=None):
+        """restore_testsets.py:53-79 on device. img_u8 [B,H,W,3] uint8 (RGB) -> restored uint8 [B,H,W,3].
+        verdict: None, or a device int32 [B] (ops.degradation_stats_u8): image b is restored where
+        verdict[b] == 1 and returned unchanged where it is 0, chosen on the device (mx_det.gate)."""
         B, H, W, _ = img_u8.shape
         ph, pw = (16 - H % 16) % 16, (16 - W % 16) % 16
         Hp, Wp = H + ph, W + pw
@@ -222,5 +224,11 @@ class RestorationUNet(nn.Module):
                                std=(1.0, 1.0, 1.0))
         r = self.residual_nhwc(x8)
         out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=img_u8.device)
-        call("mx_restore_finish", _p(src), B, Hp, Wp, _p(r), H, W, _p(out), _s())
+        if verdict is None:
+            call("mx_restore_finish", _p(src), B, Hp, Wp, _p(r), H, W, _p(out), _s())
+        else:
+            if not (torch.is_tensor(verdict) and verdict.dtype == torch.int32 and tuple(verdict.shape) == (B,)
+                    and verdict.is_contiguous() and verdict.device == img_u8.device):
+                raise RuntimeError("restore_u8: verdict must be a contiguous int32 [B] tensor on the images' device")
+            call("mx_restore_finish_gated", _p(src), B, Hp, Wp, _p(r), H, W, _p(verdict), _p(out), _s())
         return out

@@ -49,7 +49,10 @@ def variant_paths(root, v):
     return str(root / v / "images" / "val"), str(root / v / "annotations" / "instances_val.json")
 
 
-def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None):
+def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None, restore_clean=False, counts=None):
+    """restore_clean: apply `restorer` to Test_Clean as well (a blind mx_det.gate.GatedRestorer decides per
+    image, so the directory name no longer does). counts: a dict that receives the restorer's
+    take_counts() per variant (this rank's shard)."""
     rank = dist_info()[1]
     root = COCO_TESTSET_ROOT if root is None else root
     variants = all_variants() if variants is None else variants
@@ -59,7 +62,9 @@ def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None):
     res = {}
     for v in variants:
         img_dir, ann = variant_paths(root, v)
-        m = eval_frcnn_variant(model, img_dir, ann, dev, restorer=restorer if v != "Test_Clean" else None)
+        m = eval_frcnn_variant(model, img_dir, ann, dev, restorer=restorer if restore_clean or v != "Test_Clean" else None)
+        if counts is not None and restorer is not None:
+            counts[v] = restorer.take_counts()
         if rank == 0:
             res[v] = m
             print(f"  [{short(v)}] mAP50={m['mAP50']:.4f}  mAP50-95={m['mAP50_95']:.4f}", flush=True)

@@ -10,6 +10,12 @@ restored by the HIP U-Net on the GPU (reflect pad, /255, U-Net, *255, clip, trun
 straight to detection, no host round trip and no JPEG re-encode. That skips the reference's JPEG
 round trip, so its mAP is not the reference's number: it goes to
 experiments/eval_restored_results_fused.json instead.
+MX_RESTORE_GATE (with MX_RESTORE_ON_DEVICE=1; unset or 0: off, auto: mx_det.gate.DEFAULT_RULES, else the path
+of a rules JSON such as scripts.fit_restore_gate writes): the blind gate in front of the U-Net. Every image
+of every variant, Test_Clean included, gets its degradation statistics on the device and is restored or
+passed through by their verdict (mx_det.gate.GatedRestorer, mode select: no host synchronisation). Results
+go to experiments/eval_restored_results_gated.json (reference schema), the per-variant restored / passed
+counts to experiments/restore_gate_counts.json.
 MX_EXTRA_VARIANTS=jpeg evaluates the restored Test_JPEG set too, MX_SEVERITIES the restored
 Test_<Kind>_s<L> sets (eval_all.all_variants()).
 """
@@ -18,6 +24,7 @@ from pathlib import Path
 
 import torch
 
+from mx_det import gate
 from mx_det.unet import RestorationUNet
 from scripts import eval_all
 
@@ -37,20 +44,34 @@ def load_unet(dev, ckpt=None):
     return unet.to(dev).eval()
 
 
+def results_name(on_device, gated=False):
+    if on_device and gated:
+        return "eval_restored_results_gated.json"
+    return "eval_restored_results_fused.json" if on_device else "eval_restored_results.json"
+
+
 def main():
     dev, world, rank = eval_all.init_device()
     on_device = os.environ.get("MX_RESTORE_ON_DEVICE", "0") != "0"
+    rules = gate.env_gate() if on_device else None  # a bad rules file raises here, before any model loads
     restorer = load_unet(dev) if on_device else None
     root = CORRUPTED_ROOT if on_device else RESTORED_ROOT
-    results = {}
+    results, counts = {}, {}
+    kw = {}
+    if rules is not None:
+        restorer = gate.GatedRestorer(restorer, rules[0], rules[1], mode="select")
+        kw = dict(restore_clean=True)
     for name, ck in CKPTS.items():
-        r = eval_all.eval_model(name, ck, dev, root=root, restorer=restorer)
+        if rules is not None:
+            kw["counts"] = counts.setdefault(name, {})
+        r = eval_all.eval_model(name, ck, dev, root=root, restorer=restorer, **kw)
         if rank == 0:
             results[name] = r
     if rank == 0:
         OUT_DIR.mkdir(parents=True, exist_ok=True)
-        name = "eval_restored_results_fused.json" if on_device else "eval_restored_results.json"
-        eval_all.save_json(results, OUT_DIR / name)
+        eval_all.save_json(results, OUT_DIR / results_name(on_device, rules is not None))
+        if rules is not None:
+            eval_all.save_json(counts, OUT_DIR / "restore_gate_counts.json")
     return results
 
 

@@ -8,6 +8,10 @@ MX_JPEG_ENCODE=host encodes with PIL instead; MX_JPEG_DECODE=device decodes the 
 too (the default decodes it on the host). The fused eval path (eval_restored.py) skips this step.
 MX_EXTRA_VARIANTS=jpeg restores Test_JPEG as well (night, haze, rain: Test_Night, Test_Haze, Test_Rain),
 MX_SEVERITIES the Test_<Kind>_s<L> sets.
+MX_RESTORE_GATE (unset or 0: off, auto, or a rules JSON; mx_det.gate): the blind gate decides per image. An
+image it passes is copied as a file (shutil.copy2: no JPEG round trip), one it flags is restored and encoded
+as above; Test_Clean goes through the gate like the others. Output goes to data/testsets/coco6_gated, the
+per-variant restored / passed counts are printed.
 """
 import os
 import shutil
@@ -18,12 +22,13 @@ import torch
 from PIL import Image
 
 from scripts import eval_restored
-from mx_det import jpeg
+from mx_det import gate, jpeg
 from mx_det.augment import env_extra_variants, severity_variants
 from mx_det.engine import init_device
 
 COCO_TESTSET_ROOT = Path("data/testsets/coco6")
 COCO_OUT_ROOT = Path("data/testsets/coco6_restored")
+COCO_GATED_ROOT = Path("data/testsets/coco6_gated")
 VARIANTS_TO_RESTORE = ["Test_Noise", "Test_Blur", "Test_LowRes"]
 
 
@@ -51,6 +56,8 @@ def write_rgb(path, img):
 
 
 def restore_variant(unet, variant, dev, src_root=None, dst_root=None):
+    """unet: a RestorationUNet, or a gate.GatedRestorer (mode skip) that decides per image."""
+    gated = isinstance(unet, gate.GatedRestorer)
     src_root = COCO_TESTSET_ROOT if src_root is None else src_root
     dst_root = COCO_OUT_ROOT if dst_root is None else dst_root
     src_img, dst_img = src_root / variant / "images" / "val", dst_root / variant / "images" / "val"
@@ -61,14 +68,29 @@ def restore_variant(unet, variant, dev, src_root=None, dst_root=None):
         shutil.copy2(f, dst_ann / f.name)
     files = sorted(src_img.glob("*.jpg"))
     for i, p in enumerate(files):
-        write_rgb(dst_img / p.name, unet.restore_u8(read_rgb(p, dev)[None])[0])
+        img = read_rgb(p, dev)[None]
+        verdict = 1
+        if gated:  # skip mode, with the file itself as the passed image's copy
+            verdict = unet.decide_u8(img)[0]
+            unet.count([verdict])
+        if verdict:
+            write_rgb(dst_img / p.name, (unet.unet if gated else unet).restore_u8(img)[0])
+        else:
+            shutil.copy2(p, dst_img / p.name)
         if (i + 1) % 100 == 0 or i + 1 == len(files):
             print(f"    COCO {variant}: {i + 1}/{len(files)}", flush=True)
 
 
 def main():
     dev, _, _ = init_device()
+    rules = gate.env_gate()  # a bad rules file raises here
     unet = eval_restored.load_unet(dev)
+    if rules is not None:
+        gated = gate.GatedRestorer(unet, rules[0], rules[1], mode="skip")
+        for v in ["Test_Clean"] + variants_to_restore():
+            restore_variant(gated, v, dev, dst_root=COCO_GATED_ROOT)
+            print(f"    gate {v}: {gated.take_counts()}", flush=True)
+        return
     for v in variants_to_restore():
         restore_variant(unet, v, dev)
     clean_src, clean_dst = COCO_TESTSET_ROOT / "Test_Clean", COCO_OUT_ROOT / "Test_Clean"
