@@ -661,8 +661,9 @@ extern "C" int mx_bn_finalize_ex(const float* stats, int64_t mb, int64_t K, int6
 extern "C" int mx_bn_bwd_finalize(const float* part, int64_t mb, int64_t K, int64_t M, const float* mean,
                                   const float* invstd, const float* gamma, float* sums, float* coef, void* ws,
                                   size_t ws_bytes, mx_stream_t stream) {
-  MX_CHECK_ARG(mb > 0 && K > 0 && M > 0 && part && mean && invstd && sums && coef, "bn_bwd_finalize: bad arguments");
+  MX_CHECK_ARG(mb > 0 && K > 0 && M > 0, "bn_bwd_finalize: bad sizes");
   MX_CHECK_ARG(cdiv(K, 64) <= MAX_CHUNKS, "bn_bwd_finalize: K > %d", MAX_CHUNKS * 64);
+  MX_CHECK_ARG(part && mean && invstd && sums && coef, "bn_bwd_finalize: bad arguments");
   const size_t need = mx_bn_finalize_workspace(mb, K);
   MX_CHECK_ARG(ws && ws_bytes >= need, "bn_bwd_finalize: workspace of %zu bytes required (mx_bn_finalize_workspace)",
                need);
@@ -692,6 +693,8 @@ extern "C" int mx_bn_apply(const void* x, int xdtype, int64_t M, int64_t K, cons
                            const void* residual, int act, void* y, int ydtype, mx_stream_t stream) {
   MX_CHECK_ARG(K % 8 == 0, "bn_apply: K %% 8 != 0");
   MX_CHECK_ARG((xdtype == MX_BF16 || xdtype == MX_F32) && (ydtype == MX_BF16 || ydtype == MX_F32), "bn_apply: bad dtype");
+  MX_CHECK_ARG(!(xdtype == MX_BF16 && ydtype == MX_F32),
+               "bn_apply: bf16 input with f32 output is not a supported combination");
   if (M == 0) return MX_OK;
   const unsigned grid = grid_rows(M, K / 8);
   hipStream_t st = (hipStream_t)stream;
@@ -737,9 +740,9 @@ extern "C" int mx_bn_bwd_reduce_ex(const void* dy, const void* y, const void* x,
   MX_CHECK_ARG(act >= 0 && act <= 2, "bn_bwd_reduce: act 0/1/2");
   MX_CHECK_ARG(act == 0 || y, "bn_bwd_reduce: y required for an activation");
   BwdGeo g = bwd_geo(M, K);
+  MX_CHECK_ARG(g.gy <= MAX_CHUNKS && g.RB < 65536, "bn_bwd_reduce: K > %d", MAX_CHUNKS * 64);
   const size_t need = mx_bn_bwd_workspace(M, K);
   MX_CHECK_ARG(ws && ws_bytes >= need, "bn_bwd_reduce: workspace of %zu bytes required (mx_bn_bwd_workspace)", need);
-  MX_CHECK_ARG(g.gy <= MAX_CHUNKS && g.RB < 65536, "bn_bwd_reduce: K > %d", MAX_CHUNKS * 64);
   unsigned* ctr = (unsigned*)ws;
   float* part = (float*)((char*)ws + CTR_BYTES);
   MX_DT_DISPATCH(dtype, bn_bwd_reduce_launch, dy, y, x, M, K, act, g, mean, invstd, gamma, ctr, part, sums, coef,
