@@ -623,6 +623,41 @@ int mx_conv2d_dgrad_x3(const mx_conv_shape* s, const float* dy, const uint16_t* 
 int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const float* x, float* dw, int64_t Kout, int64_t Cin,
                        int layout, void* ws, size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg);
 
+/* Row-sparse backward of the RPN head (Faster R-CNN training: the RPN loss gives a gradient to at
+ * most B = batch_size_per_image sampled anchors per image, every other element of the raw head maps'
+ * gradient is an exact zero).
+ * mx_rpn_rows_build: from the gradient g of a raw head map [N][H][W][C] f32, the ascending lists of
+ * flat pixel indices (n*H + h)*W + w of S0 = pixels with any nonzero bit pattern among their C values
+ * (the sign bit ignored: -0.0 does not mark), S1 = S0 dilated by the 3x3 neighbourhood clipped to
+ * the pixel's own image, S2 = S1 dilated again; `levels` (1..3) of them are built into rows0..2 of
+ * capacities cap0..2 (<= N*H*W; mx_rpn_rows_capacity(P, N*B, level) = min(P, N*B * {1, 9, 25})).
+ * counts[l] = the true number of pixels of list l; a list longer than its capacity is cut there
+ * (nothing is written past it) and *flag is set to 1 (sticky: never cleared by the library).
+ * ws: mx_rpn_rows_workspace(N*H*W) bytes. No atomics, no sort: a bitmap per list and an ordered
+ * popcount scan, so the result is deterministic.
+ * mx_rpn_tiles_build: the same three sets as ascending lists of the 32-pixel K-steps that hold one of
+ * their pixels (index p / 32 over the flat pixels: the aligned groups the x3 wgrad kernel multiplies
+ * per MFMA step), capacities mx_rpn_tiles_capacity(P, N*B, level) = min(ceil(P / 32), N*B * {1, 6, 10});
+ * counts, overflow, flag and workspace as above.
+ * mx_conv2d_wgrad_x3_rows: mx_conv2d_wgrad_x3 (128 x 128 kernel: cfg NULL or wgrad_variant 3; others
+ * are refused) with the same cfg, geometry, workspace (mx_conv_workspace_x3 pass 2) and split
+ * partials, each block running only those K-steps of its split that tiles / ntiles list
+ * (min(*ntiles, cap) entries of an mx_rpn_tiles_build list are read). dy stays the dense-addressed
+ * [N][Ho][Wo][K] map and must be zero in every K-step not listed: a skipped step would have added
+ * exact zeros to every accumulator, so for finite operands dw equals mx_conv2d_wgrad_x3's bit for bit. */
+int64_t mx_rpn_rows_capacity(int64_t P, int64_t NB, int level);
+size_t mx_rpn_rows_workspace(int64_t P);
+int mx_rpn_rows_build(const float* g, int64_t N, int64_t H, int64_t W, int64_t C, int levels, int32_t* rows0,
+                      int64_t cap0, int32_t* rows1, int64_t cap1, int32_t* rows2, int64_t cap2, int32_t* counts,
+                      int32_t* flag, void* ws, size_t ws_bytes, mx_stream_t stream);
+int64_t mx_rpn_tiles_capacity(int64_t P, int64_t NB, int level);
+int mx_rpn_tiles_build(const float* g, int64_t N, int64_t H, int64_t W, int64_t C, int levels, int32_t* tiles0,
+                       int64_t cap0, int32_t* tiles1, int64_t cap1, int32_t* tiles2, int64_t cap2, int32_t* counts,
+                       int32_t* flag, void* ws, size_t ws_bytes, mx_stream_t stream);
+int mx_conv2d_wgrad_x3_rows(const mx_conv_shape* s, const float* dy, const float* x, float* dw, int64_t Kout,
+                            int64_t Cin, int layout, const int32_t* tiles, const int32_t* ntiles, int64_t cap, void* ws,
+                            size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg);
+
 /* NHWC pooling / resampling (dtype MX_BF16 or MX_F32 storage, C % 8 == 0).
  * maxpool: F.max_pool2d (ResNet stem k3 s2 p1 — torchvision resnet50 reached at
  *   train_frcnn_baseline.py:139; U-Net MaxPool2d(2), restoration_net.py:39); argmax (nullable,

@@ -20,6 +20,7 @@
 #include "mx_common.h"
 #include "mx_conv_layout.h"
 #include "mx_dma.h"
+#include "mx_rpn_rows.h"
 
 #include <vector>
 
@@ -1081,7 +1082,19 @@ struct WgP {
   int64_t Kout, Cin;   // real (unpadded) output / input channels written to dw
   int layout;
   int dC, dRS;         // dw's (channels per tap, taps): = (C, R*S) unless a dense conv runs as a 1x1 GEMM
+  // tile-list form (mx_conv2d_wgrad_x3_rows): each split visits only the 32-pixel K-steps listed in
+  // rows[0 .. min(*nrows, rows_cap)) (ascending indices p / 32 of the K-steps that hold a pixel with a
+  // nonzero dy row) instead of all of its K-steps; null = every K-step
+  const int32_t* rows;
+  const int32_t* nrows;
+  int64_t rows_cap;
 };
+
+// listed K-steps of a tile-list wgrad: the device count cut at the list's capacity
+__device__ __forceinline__ int64_t wgrad_rows(const WgP& p) {
+  const int64_t n = *p.nrows;
+  return n < 0 ? 0 : (n < p.rows_cap ? n : p.rows_cap);
+}
 
 // dw element (k, col = tap*C + c) -> its offset in the requested layout, or -1 for padding
 __device__ __forceinline__ int64_t wgrad_dst(const WgP& p, int64_t k, int col) {
@@ -1888,8 +1901,14 @@ __global__ void __launch_bounds__(64 * WR * WC, OCC) conv_x3_buf_kernel(ConvP p)
 // into hi / lo while staged (register loads, 32-pixel K-tiles, pixel-major bf16 LDS tiles with the
 // swz_w swizzle), fragments read transposed with ds_read_b64_tr_b16 as in conv_wgrad_buf_kernel;
 // 128 x 128 (k, col) block tiles, the pixel axis split into slab partials (wgrad_reduce_kernel).
-__global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_kernel(WgP p) {
+// ROWS: the tile-list form -- the same splits and the same 32-pixel K-steps at the same positions, but a
+// block runs only those of its K-steps that p.rows lists (the others multiply all-zero dy rows: an
+// MFMA step that adds exact zeros to every accumulator), one index load and its (n, oh, ow) decode
+// per K-step in place of the carries. Every accumulator sees the same nonzero terms in the same
+// order as in the dense kernel, so the result is the dense kernel's bit for bit (finite operands).
 #if defined(__HIP_DEVICE_COMPILE__)
+template <bool ROWS>
+__device__ __forceinline__ void wgrad_x3_body(const WgP& p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int PXT = 32, OPB = PXT * 256, STAGE = 4 * OPB;  // planes: dy hi, dy lo, x hi, x lo
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1905,6 +1924,23 @@ __global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_kernel(WgP p) {
   const int64_t pbeg = split * p.kchunk;
   const int64_t pend = min<int64_t>(p.P, pbeg + p.kchunk);
   if (pbeg >= pend) return;
+  // ROWS: [li, lend) = this split's entries of the K-step list (pbeg and kchunk are multiples of PXT)
+  int li = 0, lend = 0;
+  if constexpr (ROWS) {
+    const int n = (int)wgrad_rows(p);
+    const int tb = (int)(pbeg / PXT), te = (int)((pend + PXT - 1) / PXT);
+    auto lower = [&](int v) {
+      int lo = 0, hi = n;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (p.rows[mid] < v) lo = mid + 1;
+        else hi = mid;
+      }
+      return lo;
+    };
+    li = lower(tb);
+    lend = lower(te);
+  }
   const float* __restrict__ dy = (const float*)p.dy;
   const float* __restrict__ x = (const float*)p.x;
   const int ch = tid & 15;  // this thread's 8-wide chunk of the k columns (dy) and of the (r,s,c) columns (x)
@@ -1941,8 +1977,16 @@ __global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_kernel(WgP p) {
   auto load = [&]() {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
+      if constexpr (ROWS) {  // load() runs once per listed K-step: li < lend here
+        px_i[i] = p.rows[li] * PXT + (tid >> 4) + 16 * i;
+        const int t = px_i[i] / OW;
+        px_ow[i] = px_i[i] - t * OW;
+        px_n[i] = t / OH;
+        px_oh[i] = t - px_n[i] * OH;
+      }
       const bool pok = px_i[i] < pend32;
-      const uint32_t od = (pok && k_ok) ? __umul24((uint32_t)px_i[i], (uint32_t)(p.K * 4)) + dy_col : kOOB;
+      const int pix = px_i[i];
+      const uint32_t od = (pok && k_ok) ? __umul24((uint32_t)pix, (uint32_t)(p.K * 4)) + dy_col : kOOB;
       const int ih = __mul24(px_oh[i], p.st_h) + ihb, iw = __mul24(px_ow[i], p.st_w) + iwb;
       const bool xok = pok && col_ok && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W;
       const uint32_t ox = xok ? (uint32_t)__mul24(__mul24(px_n[i], H) + ih, W) + (uint32_t)iw : 0u;
@@ -1953,6 +1997,7 @@ __global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_kernel(WgP p) {
       rx[i][1] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xr, oxb + 16u, 0, 0));
       // advance PXT pixels: branch-free carries (ow < OW, oh < OH stay invariant)
       px_i[i] += PXT;
+      if constexpr (ROWS) continue;
       int ow = px_ow[i] + dw;
       const int c1 = ow >= OW ? 1 : 0;
       ow -= c1 * OW;
@@ -1963,6 +2008,7 @@ __global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_kernel(WgP p) {
       px_oh[i] = oh;
       px_n[i] += dn + c2;
     }
+    if constexpr (ROWS) ++li;
   };
   auto store = [&](int buf) {
     char* Dh = smem + buf * STAGE;
@@ -1995,7 +2041,11 @@ __global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_kernel(WgP p) {
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int64_t nk = (pend - pbeg + PXT - 1) / PXT;
+  const int64_t nk = ROWS ? (int64_t)(lend - li) : (pend - pbeg + PXT - 1) / PXT;
+  if (ROWS && nk == 0) {  // no listed K-step in this split: its partial is the zero the dense kernel sums
+    wgrad_store(p, acc, k0, c0, wm, wn, lane, split);
+    return;
+  }
   load();
   store(0);
   __syncthreads();
@@ -2026,6 +2076,18 @@ __global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_kernel(WgP p) {
     __syncthreads();
   }
   wgrad_store(p, acc, k0, c0, wm, wn, lane, split);
+}
+#endif
+__global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_kernel(WgP p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  wgrad_x3_body<false>(p);
+#endif
+}
+// Tile-list bf16x3 wgrad (mx_conv2d_wgrad_x3_rows): conv_wgrad_x3_kernel's geometry and partials, each
+// block running only the listed K-steps of its split.
+__global__ void __launch_bounds__(NT, 2) conv_wgrad_x3_rows_kernel(WgP p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  wgrad_x3_body<true>(p);
 #endif
 }
 
@@ -2665,7 +2727,7 @@ extern "C" int mx_conv_set_korder(int v) {
 // [4] output tiles, [5] 1 = buffer-descriptor kernel, [6] kernel kind (bf16 fwd/dgrad: the variant
 // 0..9 launched; bf16 wgrad: 0 px32, 1 px64, 2 direct-to-LDS, 3 buffer; bf16x3: 100 + the ring /
 // wave-tile alternative (mx_conv_set_stages) for fwd/dgrad, 100 + 3 / 4 / 5 (128x128, 128x256,
-// 256x256 block) for wgrad), [7] launches issued by the entry so far (dgrad: non-empty parity classes)
+// 256x256 block) for wgrad, 106 the tile-list 128x128 wgrad), [7] launches issued by the entry so far (dgrad: non-empty parity classes)
 static thread_local int32_t g_last_launch[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
 static thread_local int32_t g_launch_count = 0;  // reset by each entry point, counted per launch
 static void record_launch(int pass, int bmt, int bn, int64_t splits, int64_t tiles, bool buf, int kind) {
@@ -3440,6 +3502,60 @@ extern "C" int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const
   record_launch(2, ww ? 256 : 128, (ww || wide) ? 256 : 128, g.splits, g.tiles, true, 100 + (ww ? 5 : wide ? 4 : 3));
   if (g.splits > 1) {
     MX_CHECK_ARG(Kout < 65536, "conv wgrad x3: too many output channels for the split reduce");
+    wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);
+    MX_LAUNCH_CHECK();
+  }
+  return MX_OK;
+}
+
+extern "C" int mx_conv2d_wgrad_x3_rows(const mx_conv_shape* s, const float* dy, const float* x, float* dw, int64_t Kout,
+                                       int64_t Cin, int layout, const int32_t* tiles, const int32_t* ntiles, int64_t cap,
+                                       void* ws, size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  if (rc) return rc;
+  rc = conv_check(s);
+  if (rc) return rc;
+  MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "conv wgrad x3 rows: K and C must be multiples of 8");
+  MX_CHECK_ARG(Kout >= 1 && Kout <= s->K && Cin >= 1 && Cin <= s->C, "conv wgrad x3 rows: Kout/Cin out of range");
+  MX_CHECK_ARG(layout == 0 || layout == 1, "conv wgrad x3 rows: layout 0 (KRSC) or 1 (KCRS)");
+  MX_CHECK_ARG(s->K * s->R * s->S * s->C < (1ll << 31), "conv wgrad x3 rows: weight too large");
+  MX_CHECK_ARG(dy && x && dw && tiles && ntiles, "conv wgrad x3 rows: null operand");
+  MX_CHECK_ARG(!wgrad_x3_wide(cf) && !wgrad_x3_ww(cf),
+               "conv wgrad x3 rows: only the 128 x 128 kernel (wgrad_variant 3) has a tile-list form");
+  bool dense;
+  wgrad_shape(s, &dense);
+  MX_CHECK_ARG(!dense, "conv wgrad x3 rows: a dense (FC-style) conv has no pixel axis to list");
+  WgP p{};
+  p.dy = (const uint16_t*)(const void*)dy; p.x = (const uint16_t*)(const void*)x; p.dw = dw;
+  p.P = s->N * s->Ho * s->Wo; p.K = s->K; p.Ncol = s->R * s->S * s->C;
+  p.OH = s->Ho; p.OW = s->Wo; p.H = s->H; p.W = s->W; p.C = s->C; p.N = s->N;
+  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
+  p.Kout = Kout; p.Cin = Cin; p.layout = layout;
+  p.dC = (int)s->C; p.dRS = (int)(s->R * s->S);
+  MX_CHECK_ARG(cap >= 0 && cap <= cdiv(p.P, 32), "conv wgrad x3 rows: capacity %lld outside [0, %lld]", (long long)cap,
+               (long long)cdiv(p.P, 32));
+  // mx_conv2d_wgrad_x3's geometry for the same cfg: the same splits, so the same partial sums
+  const WGeo g = wgrad_geo_x3(cf, s);
+  p.kchunk = g.kchunk;
+  p.rows = tiles; p.nrows = ntiles; p.rows_cap = cap;
+  if (g.splits > 1) {
+    const size_t need = sizeof(float) * (size_t)g.splits * p.K * p.Ncol;
+    MX_CHECK_ARG(ws && ws_bytes >= need, "conv wgrad x3 rows: split workspace of %zu bytes required (mx_conv_workspace_x3)",
+                 need);
+    p.slab = (float*)ws;
+  }
+  MX_CHECK_ARG(g.tiles * g.splits < (1ll << 31), "conv wgrad x3 rows: grid too large");
+  MX_CHECK_ARG(p.P * p.K * 4 < (1ll << 31) && p.N * p.H * p.W * p.C * 4 < (1ll << 31) && p.P + 64 < (1ll << 23) &&
+                   p.N * p.H * p.W < (1ll << 23) && p.K * 4 < (1ll << 24) && p.C * 4 < (1ll << 24),
+               "conv wgrad x3 rows: dy / x must each stay below 2 GiB and 8M pixels (32-bit / 24-bit offset math)");
+  hipStream_t st = (hipStream_t)stream;
+  conv_wgrad_x3_rows_kernel<<<(unsigned)(g.tiles * g.splits), NT, 2 * 4 * 32 * 256, st>>>(p);
+  MX_LAUNCH_CHECK();
+  g_launch_count = 0;
+  record_launch(2, 128, 128, g.splits, g.tiles, true, 106);
+  if (g.splits > 1) {
+    MX_CHECK_ARG(Kout < 65536, "conv wgrad x3 rows: too many output channels for the split reduce");
     wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);
     MX_LAUNCH_CHECK();
   }

@@ -236,6 +236,15 @@ _SIGS = {
                                    c_vp, c_i64, c_vp, c_sz, c_vp, c_cfg]),
     "mx_conv2d_wgrad_x3": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_sz,
                                    c_vp, c_cfg]),
+    "mx_rpn_rows_capacity": (c_i64, [c_i64, c_i64, c_int]),
+    "mx_rpn_rows_workspace": (c_sz, [c_i64]),
+    "mx_rpn_rows_build": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                  c_vp, c_vp, c_sz, c_vp]),
+    "mx_rpn_tiles_capacity": (c_i64, [c_i64, c_i64, c_int]),
+    "mx_rpn_tiles_build": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                   c_vp, c_vp, c_sz, c_vp]),
+    "mx_conv2d_wgrad_x3_rows": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp,
+                                        c_i64, c_vp, c_sz, c_vp, c_cfg]),
     "mx_coco_match": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
                               c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mx_coco_accumulate_workspace": (c_sz, [c_i64]),

@@ -129,8 +129,8 @@ class HipBackend:
     def bnb_link():
         return mc.BNBLink()
 
-    def conv(self, x, weight, bias, stride, pad, act, out_dtype=None):
-        return mc.ConvAct.apply(x, weight, bias, stride, pad, act, out_dtype)
+    def conv(self, x, weight, bias, stride, pad, act, out_dtype=None, rows=None):
+        return mc.ConvAct.apply(x, weight, bias, stride, pad, act, out_dtype, rows)
 
     def maxpool(self, x, k, stride, pad):
         return _MaxPool.apply(x, k, stride, pad)

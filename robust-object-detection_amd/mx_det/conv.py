@@ -574,7 +574,7 @@ def wgrad_stream(device):
     return dedicated_stream(device, "wgrad")
 
 
-def _wgrad_plan(ctx, dy, x, K, R, S, stride, pad, kout=None, cin=None):
+def _wgrad_plan(ctx, dy, x, K, R, S, stride, pad, kout=None, cin=None, rows=None):
     """A conv backward's weight gradient, decided before its dgrad is launched: (job or its arguments,
     side, fork event) for _wgrad_run after the dgrad, or None when the weight needs no gradient.
 
@@ -592,11 +592,11 @@ def _wgrad_plan(ctx, dy, x, K, R, S, stride, pad, kout=None, cin=None):
     dst = grad_dest(ctx)
     side = side_wgrad_enabled(ctx)
     if side and os.environ.get("MX_WGRAD_FORK", "early") != "late":
-        job = wgrad_prepare(dy, x, K, R, S, stride, pad, kout, cin, dst)
+        job = wgrad_prepare(dy, x, K, R, S, stride, pad, kout, cin, dst, rows)
         fork = torch.cuda.Event()
         fork.record()
         return job, side, fork
-    return (dy, x, K, R, S, stride, pad, kout, cin, dst), side, None
+    return (dy, x, K, R, S, stride, pad, kout, cin, dst, rows), side, None
 
 
 def _wgrad_run(plan):
@@ -618,10 +618,10 @@ class _WgradJob:
     split workspace allocated, so the launch itself allocates nothing. cfg: the ConvCfg of the tuner's
     pick (None: the library's process defaults) that sized the workspace and goes to the launch."""
     __slots__ = ("sh", "x3", "entry", "dw", "dyc", "x", "ws", "wsb", "cfg", "kout", "cin", "K", "R", "S", "stride",
-                 "t0")
+                 "t0", "rows")
 
 
-def wgrad_prepare(dy, x, K, R, S, stride, pad, kout=None, cin=None, out=None):
+def wgrad_prepare(dy, x, K, R, S, stride, pad, kout=None, cin=None, out=None, rows=None):
     """Everything of conv_wgrad before the launch: on the current stream (allocations, dy.contiguous(),
     the tuner's first trial of the shape). A side-stream launch forked BEFORE the dgrad (_wgrad_plan)
     needs these done first: a workspace allocated after the dgrad could reuse the dgrad's just-freed
@@ -644,6 +644,7 @@ def wgrad_prepare(dy, x, K, R, S, stride, pad, kout=None, cin=None, out=None):
     j.x = x
     j.dyc = dyc = dy.contiguous()
     j.t0 = _timer.start() if _timer else None
+    j.rows = None
     key = ("wgrad", x.dtype, sh.N, sh.H, sh.W, x.shape[3], K, R, S, tuple(stride), tuple(pad))
     def trial(c):  # timed on the current stream; the real launch may go to the side stream
         cfg_ = _wg_cfg(c)
@@ -654,6 +655,11 @@ def wgrad_prepare(dy, x, K, R, S, stride, pad, kout=None, cin=None, out=None):
     j.cfg = _wg_cfg(_pick(key, _WG_CANDS_X3 if x3 else _WG_CANDS, trial) if _tune_on() else None)
     j.wsb = getattr(_lib.load(), wsfn)(ctypes.byref(sh), 2, j.cfg)
     j.ws = torch.empty(j.wsb, dtype=torch.uint8, device=x.device) if j.wsb else None
+    if rows is not None and x3 and (j.cfg is None or j.cfg.wgrad_variant == 3):
+        # tile-list form (RowLists.level) of the dense launch this shape would get: the same cfg,
+        # splits and workspace, only the K-steps that hold a listed pixel are run -- the same bits.
+        # The wide-tile picks (variants 4 / 5) have no such form and run densely.
+        j.rows, j.entry = rows, "mx_conv2d_wgrad_x3_rows"
     return j
 
 
@@ -669,7 +675,13 @@ def wgrad_launch(j, side=False, fork=None):
         else:
             st.wait_stream(torch.cuda.current_stream())
         stream = st.cuda_stream
-    call(j.entry, ctypes.byref(j.sh), _p(j.dyc), _p(j.x), _p(j.dw), j.kout, j.cin, 1, _p(j.ws), j.wsb, stream, j.cfg)
+    rows = j.rows
+    if rows is not None:
+        call(j.entry, ctypes.byref(j.sh), _p(j.dyc), _p(j.x), _p(j.dw), j.kout, j.cin, 1, _p(rows[0]), _p(rows[1]),
+             rows[2], _p(j.ws), j.wsb, stream, j.cfg)
+    else:
+        call(j.entry, ctypes.byref(j.sh), _p(j.dyc), _p(j.x), _p(j.dw), j.kout, j.cin, 1, _p(j.ws), j.wsb, stream,
+             j.cfg)
     if side:
         ev = torch.cuda.Event()
         ev.record(st)
@@ -677,23 +689,27 @@ def wgrad_launch(j, side=False, fork=None):
             torch.autograd.Variable._execution_engine.queue_callback(_join_side)
         # dw itself is NOT held: AccumulateGrad adopts the tensor only while autograd holds the sole
         # reference (an extra one makes it clone dw on the main stream, before the side kernel ran)
-        _pending.append((ev, (j.dyc, j.x, j.ws)))
+        _pending.append((ev, (j.dyc, j.x, j.ws, rows)))
     dw, sh, x, dyc, K, R, S, stride, t0 = j.dw, j.sh, j.x, j.dyc, j.K, j.R, j.S, j.stride, j.t0
     x3 = j.x3
     j.dw = None
     if _timer:
-        _timer.stop(("x3_" if x3 else "") + "wgrad", 2.0 * sh.N * sh.Ho * sh.Wo * K * R * S * x.shape[3], t0,
+        # tile-list: the pixels it may visit (its capacity); the device count stays on the device
+        px = min(rows[2] * 32, sh.N * sh.Ho * sh.Wo) if rows is not None else sh.N * sh.Ho * sh.Wo
+        _timer.stop(("x3_" if x3 else "") + "wgrad", 2.0 * px * K * R * S * x.shape[3], t0,
                     _tag(sh.N, sh.H, sh.W, x.shape[3], K, R, S, stride),
                     dyc.numel() * dyc.element_size() + x.numel() * x.element_size() + dw.numel() * 4)
     return dw
 
 
-def conv_wgrad(dy, x, K, R, S, stride, pad, kout=None, cin=None, side=False, out=None):
+def conv_wgrad(dy, x, K, R, S, stride, pad, kout=None, cin=None, side=False, out=None, rows=None):
     """dy NHWC [N,Ho,Wo,K], x NHWC (both bf16, or both f32 -> bf16x3 kernels) -> dW f32
     [kout, cin, R, S] (torch weight layout; the zero-padded channels K > kout, C > cin are dropped).
     side=True (inside a backward pass only): launched on the side stream, joined at the end of the
-    backward. out: a preallocated f32 [kout, cin, R, S] destination (grad_dest)."""
-    return wgrad_launch(wgrad_prepare(dy, x, K, R, S, stride, pad, kout, cin, out), side)
+    backward. out: a preallocated f32 [kout, cin, R, S] destination (grad_dest). rows: (list, count,
+    capacity) of RowLists.level -- the f32 wgrad runs only the listed 32-pixel K-steps (dy zero
+    elsewhere): the dense launch's result bit for bit."""
+    return wgrad_launch(wgrad_prepare(dy, x, K, R, S, stride, pad, kout, cin, out, rows), side)
 
 
 def act_bias_bwd(gy, y, act, K8, need_db, g_dtype=torch.bfloat16):
@@ -844,8 +860,9 @@ class ConvAct(torch.autograd.Function):
     or None."""
 
     @staticmethod
-    def forward(ctx, x, w, b, stride, pad, act, out_dtype):
+    def forward(ctx, x, w, b, stride, pad, act, out_dtype, rows=None):
         K = w.shape[0]
+        ctx.rows = rows
         need_dx = ctx.needs_input_grad[0]
         dense = _is_dense(x.shape, w.shape[2], w.shape[3], stride, pad)
         # narrow heads (RPN cls+box 15, predictor 35): the dgrad operand is zero-padded to K8
@@ -865,8 +882,16 @@ class ConvAct(torch.autograd.Function):
         K, _, R, S = wshape
         dx = dw = db = None
         K8 = (K + 7) // 8 * 8
+        rows = None
+        if ctx.rows is not None:
+            lists, role = ctx.rows
+            if role == "src":  # the head's 1x1 conv: its gradient is the raw map's, nonzero on S0
+                lists.build(gy)
+                rows = lists.level(0, gy)
+            else:              # a tower conv: its output gradient is zero outside S<role>
+                rows = lists.level(role, gy)
         gk, db = act_bias_bwd(gy, y, act, K8, has_b and ctx.needs_input_grad[2], g_dtype=x.dtype)
-        wg = _wgrad_plan(ctx, gk, x, K8, R, S, stride, pad, kout=K, cin=wshape[1])  # before the dgrad
+        wg = _wgrad_plan(ctx, gk, x, K8, R, S, stride, pad, kout=K, cin=wshape[1], rows=rows)  # before the dgrad
         if ctx.needs_input_grad[0]:
             if _is_dense(x.shape, R, S, stride, pad):  # 1x1-GEMM form: dX[N, R*S*C] = dY[N, K8] wt
                 N, H, W, C = x.shape
@@ -885,7 +910,126 @@ class ConvAct(torch.autograd.Function):
                 dx = ctx.chain.hand(dx)
         if wg is not None:
             dw = _wgrad_run(wg)
-        return dx, dw, db, None, None, None, None
+        return dx, dw, db, None, None, None, None, None
+
+
+class RowLists:
+    """Active K-step lists of one RPN head map's backward (mx_rpn_tiles_build), handed from the head's
+    1x1 conv (role "src": its backward builds them from the raw map's gradient) to the tower convs
+    upstream of it (role 0: the last tower conv, whose output gradient is nonzero on S0 only; role 1:
+    the one before it, S1 = S0 dilated 3x3); their weight gradients, and the 1x1 conv's own (S0), then
+    run only the 32-pixel K-steps that hold a listed pixel -- the skipped ones add exact zeros, so the
+    gradients are the dense launches' bit for bit. The hand-off runs outside autograd's edges, like
+    GradChain: every conv of one map runs on one stream (checked), and the src's backward runs first
+    because it is downstream.
+
+    nb = N * batch_size_per_image bounds S0 (RegionProposalNetwork hands it to its head); a gradient
+    with more nonzero pixels -- a dense one: the graph captures' ones_like warm-ups -- overflows: the
+    lists are cut at their capacities, the device flag is set, and rows_check() raises at the step's
+    next host check unless rows_reset() cleared it (after a capture)."""
+    LEVELS = 2
+
+    def __init__(self, nb):
+        self.nb = int(nb)
+        self.lists = None
+
+    def build(self, gy):
+        assert gy.dtype == torch.float32 and gy.dim() == 4, (gy.dtype, gy.shape)
+        gy = gy.contiguous()
+        N, H, W, C = gy.shape
+        P = N * H * W
+        lib = _lib.load()
+        caps = [lib.mx_rpn_tiles_capacity(P, self.nb, l) for l in range(self.LEVELS)]
+        flag = _rows_flag(gy.device)
+        buf = torch.empty(sum(caps) + 4, dtype=torch.int32, device=gy.device)
+        rows, o = [], 0
+        for c in caps:
+            rows.append(buf[o:o + c])
+            o += c
+        counts = buf[o:o + 4]
+        wsb = lib.mx_rpn_rows_workspace(P)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=gy.device)
+        rp = [(_p(r), c) for r, c in zip(rows, caps)] + [(None, 0)] * (3 - self.LEVELS)
+        call("mx_rpn_tiles_build", _p(gy), N, H, W, C, self.LEVELS, rp[0][0], rp[0][1], rp[1][0], rp[1][1],
+             rp[2][0], rp[2][1], _p(counts), _p(flag), _p(ws), wsb, _s())
+        self.lists = (gy.shape[:3], _cur_stream(gy), [(r, counts[l:l + 1], c) for l, (r, c) in
+                                                      enumerate(zip(rows, caps))], buf)
+        _rows_watch(gy.device)
+
+    def level(self, l, gy):
+        """(K-step list, count, capacity) of S<l> for the conv whose output gradient is gy."""
+        if self.lists is None:
+            raise RuntimeError("RowLists: the head conv's backward has not built the lists")
+        nhw, st, lv, _ = self.lists
+        if tuple(gy.shape[:3]) != tuple(nhw) or _cur_stream(gy) != st:
+            raise RuntimeError("RowLists: a tower conv's gradient has another map shape or stream than the "
+                               "head conv's, whose lists it would walk")
+        return lv[l]
+
+
+_rows_flags = {}
+_rows_pending = {}
+
+
+def _rows_flag(device):
+    """The device's sticky overflow flag of the row lists (int32, zero until a list overflows)."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    f = _rows_flags.get(idx)
+    if f is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("RowLists: first use of a device inside a graph capture (warm the capture up first)")
+        f = _rows_flags[idx] = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", idx))
+        with capture_lock:  # pinned allocation: never beside an open graph capture
+            _rows_flags[idx, "host"] = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+    return f
+
+
+def _rows_watch(device):
+    """Copy the device's overflow flag to pinned memory without waiting; rows_check() reads it once a
+    later host sync has passed. Inside a capture nothing is copied: the replaying step calls
+    rows_watch after the replay."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    f = _rows_flags.get(idx)
+    if f is None or torch.cuda.is_current_stream_capturing():
+        return
+    host = _rows_flags[idx, "host"]
+    host.copy_(f, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    _rows_pending[idx] = (host, ev)
+
+
+def rows_watch(device):
+    """After a replayed backward graph that may hold row-list launches (frcnn._GraphFn)."""
+    if _rows_flags:
+        _rows_watch(torch.device(device))
+
+
+def rows_reset(device):
+    """After a graph capture: its warm-ups ran the row lists on dense ones_like gradients, which
+    overflow by design; clear the flag and forget their pending check."""
+    device = torch.device(device)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    f = _rows_flags.get(idx)
+    if f is not None:
+        f.zero_()
+        _rows_pending.pop(idx, None)
+
+
+def rows_check():
+    """Raise if a row list overflowed in a backward whose flag copy has been issued (at the latest the
+    previous step's): called where the step has just passed a host sync, so the event wait is free."""
+    for idx in list(_rows_pending):
+        pend = _rows_pending.pop(idx, None)  # a backward thread may have replaced or taken it
+        if pend is None:
+            continue
+        host, ev = pend
+        ev.synchronize()
+        if int(host) != 0:
+            _rows_flags[idx].zero_()
+            raise RuntimeError("RPN head row-sparse backward: a raw head map's gradient had more nonzero pixels than "
+                               "N * batch_size_per_image allows (a gradient that does not come from the RPN loss "
+                               "alone); its weight gradients skipped pixels. MX_RPN_SPARSE_BWD=0 selects the dense backward")
 
 
 _scratch = {}
@@ -1181,12 +1325,14 @@ class ConvNormAct(torch.nn.Sequential):
             super().__init__(conv, torch.nn.ReLU() if act == ACT_RELU else torch.nn.Identity())
         self.norm, self.act_code = norm, act
 
-    def forward(self, x, be, residual=None, bnb_own=None, bnb_feed=None):
+    def forward(self, x, be, residual=None, bnb_own=None, bnb_feed=None, rows=None):
         if self.norm:
             if bnb_own is None and bnb_feed is None:
                 return be.conv_bn(x, self[0], self[1], self.act_code, residual)
             return be.conv_bn(x, self[0], self[1], self.act_code, residual, bnb_own=bnb_own, bnb_feed=bnb_feed)
         c = self[0]
+        if rows is not None:  # (RowLists, role): a row-sparse weight gradient (HIP backend only)
+            return be.conv(x, c.weight, c.bias, c.stride, c.padding, c.act, c.out_dtype, rows=rows)
         return be.conv(x, c.weight, c.bias, c.stride, c.padding, c.act, c.out_dtype)
 
 

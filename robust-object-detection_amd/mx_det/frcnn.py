@@ -248,11 +248,30 @@ class RPNHead(nn.Module):
             x, rowh = x + w + 1, max(rowh, h)
         return pos, y + rowh, Wc
 
+    def _row_lists(self, t, be):
+        """A conv.RowLists for one map's backward when the head trains under a RegionProposalNetwork on
+        the HIP f32 path (MX_RPN_SPARSE_BWD=0: never): the RPN loss reaches at most
+        batch_size_per_image anchors per image, so the tower convs' weight gradients visit only the
+        pixels the raw map's gradient can have spread to. A head used on its own stays dense."""
+        B = self.__dict__.get("sparse_rows_per_image")
+        if (B is None or not t.is_cuda or getattr(be, "name", "") != "hip" or t.dtype != torch.float32
+                or not torch.is_grad_enabled() or t.shape[3] % 8 or os.environ.get("MX_RPN_SPARSE_BWD", "1") == "0"):
+            return None
+        return mc.RowLists(t.shape[0] * B)
+
     def _run(self, t, be, w, b, mask=None):
+        lists = self._row_lists(t, be)
+        n = len(self.conv)
         for ci, c in enumerate(self.conv):
-            t = c(t, be)
-            if mask is not None and ci + 1 < len(self.conv):
+            # the last tower conv's output gradient lives on S0, the one before it on S1 (conv.RowLists)
+            if lists is not None and n - 1 - ci < mc.RowLists.LEVELS:
+                t = c(t, be, rows=(lists, n - 1 - ci))
+            else:
+                t = c(t, be)
+            if mask is not None and ci + 1 < n:
                 t = t * mask  # zero frame between levels: the next 3x3 conv reads it as padding
+        if lists is not None:
+            return be.conv(t, w, b, (1, 1), (0, 0), ACT_NONE, out_dtype=torch.float32, rows=(lists, "src"))
         return be.conv(t, w, b, (1, 1), (0, 0), ACT_NONE, out_dtype=torch.float32)  # [N,H,W,A*5]
 
     def layout(self, feats):
@@ -468,6 +487,9 @@ class RegionProposalNetwork(nn.Module):
         self.head = head
         self.fg, self.bg = fg_iou_thresh, bg_iou_thresh
         self.fg_bg_sampler = BalancedPositiveNegativeSampler(batch_size_per_image, positive_fraction)
+        if isinstance(head, RPNHead):
+            # the sampler's bound on the anchors that get a gradient: the head's row-sparse backward
+            head.__dict__["sparse_rows_per_image"] = int(batch_size_per_image)
         self._pre = pre_nms_top_n or dict(training=2000, testing=1000)
         self._post = post_nms_top_n or dict(training=2000, testing=1000)
         self.nms_thresh, self.score_thresh, self.min_size = nms_thresh, score_thresh, min_size
@@ -1283,6 +1305,7 @@ class FasterRCNN(nn.Module):
             detections, det_losses = self.roi_heads(features, proposals, il.image_sizes, targets, be, sampled=sampled,
                                                     original_sizes=original)
             self.rpn.check_nms()
+            mc.rows_check()  # the RPN head's row lists of the previous backward (conv.RowLists)
         finally:  # also when the step raises: no side-stream work is left unjoined behind it
             self.rpn.join_losses()
         if self.training:
@@ -1425,6 +1448,7 @@ class _Graphs:
             sd = stats_module.state_dict()
             for k, v in saved.items():
                 sd[k].copy_(v)
+        mc.rows_reset(x.device)  # the ones_like warm-ups overflow the RPN head's row lists by design
         self.anchor = torch.zeros((), device=x.device, requires_grad=True)
         self.on_ready = None
 
@@ -1490,6 +1514,7 @@ class _GraphFn(torch.autograd.Function):
             if g is not None and p.grad is g:
                 p.grad = g.clone()
         tg.bwd.replay()
+        mc.rows_watch(tg.static_x.device)
         for p, g in zip(tg.params, tg.static_grads):
             if g is None:
                 continue
@@ -1581,6 +1606,7 @@ class _SegGraphs:
             sd = model.state_dict()
             for k, v in saved.items():
                 sd[k].copy_(v)
+        mc.rows_reset(x.device)  # as in _Graphs
         self.anchor = torch.zeros((), device=x.device, requires_grad=True)
         self.on_ready = None
 
@@ -1647,6 +1673,7 @@ class _SegGraphFn(torch.autograd.Function):
                     p.grad.add_(g)
             if hook is not None and ps:
                 hook(key, ps)
+        mc.rows_watch(tg.static_x.device)
         return None, None, None
 
 
