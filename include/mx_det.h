@@ -657,6 +657,34 @@ int mx_rpn_tiles_build(const float* g, int64_t N, int64_t H, int64_t W, int64_t 
 int mx_conv2d_wgrad_x3_rows(const mx_conv_shape* s, const float* dy, const float* x, float* dw, int64_t Kout,
                             int64_t Cin, int layout, const int32_t* tiles, const int32_t* ntiles, int64_t cap, void* ws,
                             size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg);
+/* mx_rpn_lists_build: what one backward step of a head map needs, from one mark and two dilations: the
+ * pixel lists S0, S1, S2 of mx_rpn_rows_build (rows0..2, counts[3]) and the K-step lists S0, S1 of
+ * mx_rpn_tiles_build (tiles0..1, tcounts[2]), each compacted from the same bitmap; capacities, cut
+ * lists, flag and workspace as for the two entries above.
+ * mx_conv2d_dgrad_x3_rows: the stride-1 mx_conv2d_dgrad_x3 on listed pixels only. rows: ascending flat
+ * pixel indices into [N][H][W] (min(*nrows, cap) entries are read; the grid is sized by cap, blocks
+ * past the count exit at once); for each listed pixel p, dx[p] = dgrad(dy)[p] (+ residual[p]) -- the
+ * same kernel instance, K order and sum as the dense launch of this shape and cfg, so the same bits;
+ * every other row of dx is left untouched (dx may be the residual buffer: an in-place add). An entry
+ * outside [0, N*H*W) is an invalid row: nothing is read or stored for it. dy is the dense-addressed
+ * map and must be zero wherever the dense gradient is. MX_EUNSUPPORTED, before any launch, when the
+ * dense launch of the shape and cfg is not an unsplit wide-wave 128- or 64-row x 128-column tile of
+ * the buffer kernel (mx_conv2d_dgrad_x3_rows_supported: 1 when it is): the caller runs the dense entry.
+ * mx_act_bias_bwd_rows: mx_act_bias_bwd (act 1, f32 in and out, K % 8 == 0) on listed rows only, on the
+ * dense launch's grid and row partition: g[r] = (gy[r] * mask[r % mask_period]) * act'(y[r]) for the
+ * listed rows r (mask nullable: no factor), other rows of g are not written; db (nullable) and the
+ * workspace as mx_act_bias_bwd. gy zero off the list: g's listed rows and db are the dense values. */
+int mx_rpn_lists_build(const float* g, int64_t N, int64_t H, int64_t W, int64_t C, int32_t* rows0, int64_t cap0,
+                       int32_t* rows1, int64_t cap1, int32_t* rows2, int64_t cap2, int32_t* counts, int32_t* tiles0,
+                       int64_t tcap0, int32_t* tiles1, int64_t tcap1, int32_t* tcounts, int32_t* flag, void* ws,
+                       size_t ws_bytes, mx_stream_t stream);
+int mx_conv2d_dgrad_x3_rows_supported(const mx_conv_shape* s, const mx_conv_cfg* cfg);
+int mx_conv2d_dgrad_x3_rows(const mx_conv_shape* s, const float* dy, const uint16_t* wt, const float* residual, float* dx,
+                            const int32_t* rows, const int32_t* nrows, int64_t cap, mx_stream_t stream,
+                            const mx_conv_cfg* cfg);
+int mx_act_bias_bwd_rows(const float* gy, const float* y, const float* mask, int64_t mask_period, int64_t M, int64_t K,
+                         const int32_t* rows, const int32_t* nrows, int64_t cap, float* g, float* db, void* ws,
+                         size_t ws_bytes, mx_stream_t stream);
 
 /* NHWC pooling / resampling (dtype MX_BF16 or MX_F32 storage, C % 8 == 0).
  * maxpool: F.max_pool2d (ResNet stem k3 s2 p1 — torchvision resnet50 reached at

@@ -8,6 +8,7 @@
 // Statistics arrive as per-block column partials from the conv epilogue (mx_conv.hip) and are
 // reduced here in f64.
 #include "mx_common.h"
+#include "mx_rpn_rows.h"
 
 namespace mx {
 
@@ -348,6 +349,71 @@ __global__ void __launch_bounds__(256) act_bias_bwd_kernel(const T* __restrict__
 #pragma unroll
       for (int t = 0; t < 8; ++t) s[t] += v[t];
       st8(g + r * K8 + c0, v);
+    }
+  }
+  if (!db) return;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) red[rl][cl * 8 + t] = s[t];
+  __syncthreads();
+  const int col = threadIdx.x & 63;
+  const int k = blockIdx.y * 64 + col;
+  if (threadIdx.x < 64) {
+    float a = 0.f;
+#pragma unroll 8
+    for (int r = 0; r < 32; ++r) a += red[r][col];
+    if (k < K) st_sc1(part + (int64_t)blockIdx.x * K + k, a);
+  }
+  if (!arrive_last(ctr + blockIdx.y, (unsigned)RB)) return;
+  __shared__ double fin[1][64], scr[256];
+  last_sums<1>((const float*)part, RB, (int64_t)K, (int64_t)blockIdx.y * 64, fin, scr);
+  if (threadIdx.x < 64 && k < K) db[k] = (float)fin[0][col];
+}
+
+// Listed-rows form of act_bias_bwd_kernel<float, 1, float> (K % 8 == 0, K8 == K): gy is nonzero only on
+// the ascending pixel list rows[0 .. min(*nrows, cap)), so a block visits only the listed rows of its
+// range [r0, r1) -- found by binary search -- each on the row lane (r - r0) % 32 of the dense loop and
+// in ascending order. The rows it skips would have added exact zeros to the lane sums, so the written
+// rows of g, the block partials and db are the dense kernel's values; unlisted rows of g are not
+// written. mask (nullable): a per-pixel factor [mask_period] repeated over the map, g = (gy * mask) * act'.
+__global__ void __launch_bounds__(256) act_bias_bwd_rows_kernel(const float* __restrict__ gy, const float* __restrict__ y,
+                                                                const float* __restrict__ mask, int64_t mask_period,
+                                                                int64_t M, int K, int64_t rows_per_block,
+                                                                const int32_t* __restrict__ rows,
+                                                                const int32_t* __restrict__ nrows, int64_t cap,
+                                                                float* __restrict__ g, float* __restrict__ db,
+                                                                unsigned* __restrict__ ctr, float* __restrict__ part) {
+  __shared__ float red[32][65];
+  __shared__ int64_t range[2];
+  const int cl = threadIdx.x & 7, rl = threadIdx.x >> 3;
+  const int c0 = blockIdx.y * 64 + cl * 8;
+  const int64_t RB = gridDim.x;
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = min<int64_t>(M, r0 + rows_per_block);
+  if (threadIdx.x < 2) {
+    const int64_t n = min<int64_t>(max<int64_t>((int64_t)*nrows, 0), cap);
+    range[threadIdx.x] = rpn_rows_lower_bound(rows, n, threadIdx.x ? r1 : r0);
+  }
+  __syncthreads();
+  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (c0 < K) {
+    const int64_t j1 = range[1];
+    for (int64_t j = range[0]; j < j1; ++j) {
+      const int64_t r = rows[j];
+      // an entry outside the block's range (a list that is not ascending) is skipped, never addressed
+      if (r < r0 || r >= r1 || (int)((r - r0) & 31) != rl) continue;
+      float v[8], vg[8], vy[8];
+      ld8(gy + r * K + c0, vg);
+      ld8(y + r * K + c0, vy);
+      if (mask) {
+        const float mk = mask[r % mask_period];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) vg[t] = vg[t] * mk;
+      }
+#pragma unroll
+      for (int t = 0; t < 8; ++t) v[t] = vg[t] * act_grad<1>(vy[t]);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) s[t] += v[t];
+      st8(g + r * K + c0, v);
     }
   }
   if (!db) return;
@@ -864,6 +930,31 @@ extern "C" int mx_act_bias_bwd(const void* gy, const void* y, int dtype, int64_t
     launch_act_bias<float, float>(gy, y, M, (int)K, (int)K8, act, g_, g, db, ctr, part, st);
   else
     MX_CHECK_ARG(false, "act_bias_bwd: bf16 input with f32 gradient output is not a supported combination");
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+extern "C" int mx_act_bias_bwd_rows(const float* gy, const float* y, const float* mask, int64_t mask_period, int64_t M,
+                                    int64_t K, const int32_t* rows, const int32_t* nrows, int64_t cap, float* g,
+                                    float* db, void* ws, size_t ws_bytes, mx_stream_t stream) {
+  MX_CHECK_ARG(M > 0 && M < (1ll << 31) && K > 0 && K % 8 == 0 && K < (1 << 24), "act_bias_bwd_rows: need M > 0, K %% 8 == 0");
+  MX_CHECK_ARG(gy && y && g && rows && nrows, "act_bias_bwd_rows: null argument");
+  MX_CHECK_ARG(cap >= 0 && cap <= M, "act_bias_bwd_rows: capacity outside [0, M]");
+  MX_CHECK_ARG(!mask || (mask_period > 0 && mask_period <= M), "act_bias_bwd_rows: mask period outside [1, M]");
+  // the dense launch's grid and row partition: the same block partials, the same f64 sum over them
+  BwdGeo g_ = act_geo(M, K);
+  MX_CHECK_ARG(g_.gy <= MAX_CHUNKS, "act_bias_bwd_rows: K > %d", MAX_CHUNKS * 64);
+  unsigned* ctr = nullptr;
+  float* part = nullptr;
+  if (db) {
+    const size_t need = mx_act_bias_bwd_workspace(M, K);
+    MX_CHECK_ARG(ws && ws_bytes >= need, "act_bias_bwd_rows: workspace of %zu bytes required (mx_act_bias_bwd_workspace)", need);
+    ctr = (unsigned*)ws;
+    part = (float*)((char*)ws + CTR_BYTES);
+  }
+  dim3 grid((unsigned)g_.RB, (unsigned)g_.gy);
+  act_bias_bwd_rows_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(gy, y, mask, mask_period, M, (int)K, g_.rows_per_block,
+                                                                  rows, nrows, cap, g, db, ctr, part);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

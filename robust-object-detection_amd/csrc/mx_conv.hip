@@ -75,6 +75,12 @@ struct ConvP {
   float* bnb_part;
   int64_t bnb_mb;
   int bnb_act;
+  // rows form of the bf16x3 dgrad (conv_x3_buf_kernel<..., ROWS>): GEMM row m is the pixel rows[m], an
+  // ascending flat index into the [N][OH][OW] grid (M stays the dense row count N*OH*OW: an entry
+  // outside [0, M) is an invalid row), min(*rows_count, rows_cap) of them
+  const int32_t* rows;
+  const int32_t* rows_count;
+  int64_t rows_cap;
 };
 
 __device__ __forceinline__ float bnb_act_grad(float y, int act) {
@@ -122,10 +128,14 @@ static constexpr int SROWS = 64;
 // WR = wave-rows of the block (2: 4 waves in 2x2, 4: 8 waves in 4x2; HALVES == WR then stages one
 // wave-row per pass).
 // WC = wave-columns (2: wave tiles of BN/2 columns; 1: each wave spans all BN columns).
-template <int BN, int HALVES = 1, int BMT = BM, typename TA = uint16_t, int WR = 2, int WC = 2, bool GROUP = false>
+// ROWS (GROUP only, no statistics / split partials): tile row m < nrows stores to the pixel p.rows[m]
+// (an entry outside [0, p.M) stores nothing), the place out_row() has for the parity remap.
+template <int BN, int HALVES = 1, int BMT = BM, typename TA = uint16_t, int WR = 2, int WC = 2, bool GROUP = false,
+          bool ROWS = false>
 __device__ __forceinline__ void conv_epilogue(const ConvP& p, f32x4 (&acc)[BMT / (16 * WR)][BN / (16 * WC)],
                                               char* smem, int64_t m0, int64_t n0, int64_t mt, int wm, int wn,
-                                              int lane, int tid, int split) {
+                                              int lane, int tid, int split, int64_t nrows = 0) {
+  static_assert(!ROWS || GROUP, "the rows form exists for the grouped (f32 dgrad) epilogue only");
   constexpr int WN = BN / WC, TJ = WN / 16, WM = BMT / WR, TI = WM / 16, NT = 64 * WR * WC;
   constexpr int PR = BMT / HALVES;  // rows staged per pass
   static_assert(HALVES == 1 || HALVES == WR, "staging: the whole tile at once, or one wave-row per pass");
@@ -273,10 +283,16 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& p, f32x4 (&acc)[BMT /
       const int row = e / CPR, cc = (e % CPR) * 8;
       int64_t m = m0 + h * PR + row;
       const int64_t col0 = n0 + cc;
-      ok[u] = k0 + u < ITER && e < PR * CPR && m < p.M && col0 < p.Ncol;
+      ok[u] = k0 + u < ITER && e < PR * CPR && m < (ROWS ? nrows : p.M) && col0 < p.Ncol;
       rw[u] = row;
       cc0[u] = col0;
-      mm[u] = ok[u] ? out_row(p, m) : 0;
+      if constexpr (ROWS) {
+        const int64_t px = ok[u] ? (int64_t)p.rows[m] : -1;
+        ok[u] = (uint64_t)px < (uint64_t)p.M;
+        mm[u] = ok[u] ? px : 0;
+      } else {
+        mm[u] = ok[u] ? out_row(p, m) : 0;
+      }
       if (ok[u] && vec) {
         if (p.residual) ld8((const TA*)p.residual + mm[u] * p.Ncol + col0, rr[u]);
         if (sizeof(TA) == 4 && p.out_f32 && p.bnb_part) {
@@ -1717,7 +1733,12 @@ __device__ __forceinline__ int x3_swz(int row) {
 // WC = 1 (wide wave tiles: WR waves stacked along M, each spanning all BN columns): every A row is
 // split by exactly one wave (WC = 2 splits each row in both wave-columns), half the split VALU per
 // MFMA, at twice the B fragment reads per wave.
-template <int BN, int MODE, int STAGES, int OCC, int BMT, int WR = 2, int WC = 2>
+// ROWS (MODE 1, stride 1, no split): the rows form -- GEMM row m is the listed pixel p.rows[m]; only the
+// prologue's (n, oh, ow) decode and the epilogue's store row differ, the K loop, K order, MFMA sequence
+// and LDS ring are the dense kernel's, so each listed output element is the dense launch's sum in its
+// order. The grid is sized by the list's capacity: a block whose first row is past the count exits
+// before any load.
+template <int BN, int MODE, int STAGES, int OCC, int BMT, int WR = 2, int WC = 2, bool ROWS = false>
 __global__ void __launch_bounds__(64 * WR * WC, OCC) conv_x3_buf_kernel(ConvP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1736,6 +1757,12 @@ __global__ void __launch_bounds__(64 * WR * WC, OCC) conv_x3_buf_kernel(ConvP p)
   const int64_t bid = gid / p.splits;
   const int64_t mt = bid / ntiles_n, nt = bid % ntiles_n;
   const int64_t m0 = mt * BMT, n0 = nt * BN;
+  int64_t nrows = p.M;  // GEMM rows of this launch
+  if constexpr (ROWS) {
+    static_assert(MODE == 1, "rows form: dgrad only");
+    nrows = min<int64_t>(max<int64_t>((int64_t)*p.rows_count, 0), p.rows_cap);
+    if (m0 >= nrows) return;
+  }
   const int lrow = lane >> 2, pc = lane & 3;  // landing row within the instruction, physical chunk
   const int qa = pc ^ x3_swz(lrow), qb = pc ^ tile_swz<4>(lrow);  // logical chunks fetched
   const int IH = (int)p.IH, IW = (int)p.IW, IC = (int)p.IC, R = p.R, S = p.S;
@@ -1743,10 +1770,15 @@ __global__ void __launch_bounds__(64 * WR * WC, OCC) conv_x3_buf_kernel(ConvP p)
   uint64_t a_mask[AI];
 #pragma unroll
   for (int i = 0; i < AI; ++i) {
-    const int64_t m = m0 + wave * AR + i * RPI + lrow;
+    int64_t m = m0 + wave * AR + i * RPI + lrow;
     uint64_t mask = 0;
     int32_t off = 0;
-    if (m < p.M) {
+    bool mok = m < nrows;
+    if constexpr (ROWS) {  // the listed pixel; an entry outside the map is an invalid row
+      m = mok ? (int64_t)p.rows[m] : -1;
+      mok = (uint64_t)m < (uint64_t)p.M;
+    }
+    if (mok) {
       const int ow = (int)(m % p.OW);
       const int64_t t = m / p.OW;
       const int oh = (int)(t % p.OH);
@@ -1892,8 +1924,8 @@ __global__ void __launch_bounds__(64 * WR * WC, OCC) conv_x3_buf_kernel(ConvP p)
   __syncthreads();
   // wide tiles stage the whole f32 tile at once (one barrier, every wave storing); 8-wave 2x2 tiles
   // stage one wave-row per pass (their whole tile would not fit beside a second block)
-  conv_epilogue<BN, (WC == 1 ? 1 : WR), BMT, float, WR, WC, MODE == 1>(p, acc, smem, m0, n0, mt, wm, wn, lane, tid,
-                                                                       split);
+  conv_epilogue<BN, (WC == 1 ? 1 : WR), BMT, float, WR, WC, MODE == 1, ROWS>(p, acc, smem, m0, n0, mt, wm, wn, lane,
+                                                                             tid, split, nrows);
 #endif
 }
 
@@ -3451,6 +3483,73 @@ extern "C" int mx_conv2d_dgrad_x3(const mx_conv_shape* s, const float* dy, const
     rc = launch_igemm_x3<1>(cf, p, make_geo_x3(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
     if (rc) return rc;
   }
+  return MX_OK;
+}
+
+// The rows form exists for the dense launch's pick when that is the buffer kernel with wide wave tiles
+// (stages 0) on an unsplit 128 x 128 or 64 x 128 tile: the instances the RPN tower dgrads run.
+static bool dgrad_x3_rows_pick(const Cfg& cf, const mx_conv_shape* s, Geo* out) {
+  if (s->stride_h != 1 || s->stride_w != 1 || s->K % 32 || s->C % 8 || s->R * s->S > 64 || s->R * s->S < 1) return false;
+  if (s->H != s->Ho || s->W != s->Wo) return false;  // listed pixels index dy's and dx's grids alike
+  const int64_t M = s->N * s->H * s->W, Kdim = s->R * s->S * s->K;
+  const bool buf = cf.loader >= 1 && cf.loader != 2 && cf.loader != 3 && M * s->K * 4 < (1ll << 31) && M > 0 &&
+                   2 * s->C * Kdim < (1ll << 30);
+  const Geo g = make_geo_x3(cf, M, s->C, Kdim);
+  if (!buf || g.splits != 1 || cf.k.stages != 0 || g.bn != 128 || (g.bmt != 128 && g.bmt != 64)) return false;
+  if (out) *out = g;
+  return true;
+}
+
+extern "C" int mx_conv2d_dgrad_x3_rows_supported(const mx_conv_shape* s, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  if (!s || resolve_cfg(cfg, cf) || conv_check(s)) return 0;
+  return dgrad_x3_rows_pick(cf, s, nullptr) ? 1 : 0;
+}
+
+extern "C" int mx_conv2d_dgrad_x3_rows(const mx_conv_shape* s, const float* dy, const uint16_t* wt, const float* residual,
+                                       float* dx, const int32_t* rows, const int32_t* nrows, int64_t cap,
+                                       mx_stream_t stream, const mx_conv_cfg* cfg) {
+  Cfg cf;
+  int rc = resolve_cfg(cfg, cf);
+  if (rc) return rc;
+  rc = conv_check(s);
+  if (rc) return rc;
+  MX_CHECK_ARG(dy && wt && dx && rows && nrows, "conv dgrad x3 rows: null operand");
+  Geo g;
+  if (!dgrad_x3_rows_pick(cf, s, &g)) {
+    set_error("conv dgrad x3 rows: the dense launch of this shape and cfg has no rows form");
+    return MX_EUNSUPPORTED;
+  }
+  DClass cl[4];
+  int64_t off[4];
+  int br[4], bs[4];
+  const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
+  MX_CHECK_ARG(n == 1 && cl[0].Hc == s->H && cl[0].Wc == s->W, "conv dgrad x3 rows: one stride-1 class expected");
+  const DClass& c = cl[0];
+  ConvP p{};
+  p.src = (const uint16_t*)(const void*)dy; p.wt = wt + c.off; p.wt_plane = s->C * s->R * s->S * s->K;
+  p.M = s->N * c.Hc * c.Wc; p.Ncol = s->C; p.Kdim = (int64_t)c.Rc * c.Sc * s->K;
+  p.OH = c.Hc; p.OW = c.Wc; p.IH = s->Ho; p.IW = s->Wo; p.IC = s->K;
+  p.R = std::max(c.Rc, 1); p.S = std::max(c.Sc, 1); p.st_h = 1; p.st_w = 1; p.pad_h = c.dh; p.pad_w = c.dw;
+  p.out = dx; p.out_f32 = 1; p.act = 0; p.residual = residual;
+  p.src_elems = s->N * s->Ho * s->Wo * s->K; p.wt_elems = p.Ncol * p.Kdim;
+  MX_CHECK_ARG(cap >= 0 && cap <= p.M, "conv dgrad x3 rows: capacity %lld outside [0, %lld]", (long long)cap, (long long)p.M);
+  MX_CHECK_ARG(p.Kdim == s->R * s->S * s->K && p.M < (1ll << 31), "conv dgrad x3 rows: unexpected class geometry");
+  p.rows = rows; p.rows_count = nrows; p.rows_cap = cap;
+  p.splits = 1; p.kt_per_split = p.Kdim / 32; p.slab = nullptr; p.korder = cf.korder;
+  g_launch_count = 0;
+  if (cap == 0) return MX_OK;
+  const int64_t blocks = rpn_rows_grid(cap, g.bmt) * cdiv(p.Ncol, (int64_t)g.bn);
+  hipStream_t st = (hipStream_t)stream;
+  if (g.bmt == 128) {
+    constexpr size_t lds = std::max<size_t>((size_t)2 * 2 * (128 + 128) * 64, (size_t)128 * (128 + 4) * 4);
+    conv_x3_buf_kernel<128, 1, 2, 2, 128, 4, 1, true><<<(unsigned)blocks, 256, lds, st>>>(p);
+  } else {
+    constexpr size_t lds = std::max<size_t>((size_t)3 * 2 * (64 + 128) * 64, (size_t)64 * (128 + 4) * 4);
+    conv_x3_buf_kernel<128, 1, 3, 2, 64, 4, 1, true><<<(unsigned)blocks, 256, lds, st>>>(p);
+  }
+  MX_LAUNCH_CHECK();
+  record_launch(1, g.bmt, g.bn, 1, blocks, true, 107);
   return MX_OK;
 }
 

@@ -46,4 +46,29 @@ inline int64_t rpn_tiles_capacity(int64_t P, int64_t NB, int level) {
   return c < T ? c : T;
 }
 
+// Row tiles of a rows-form dgrad launch: the grid is sized by the list's static capacity (the launch
+// lives in captured graphs); blocks past the device count exit at once.
+inline int64_t rpn_rows_grid(int64_t cap, int64_t tile_rows) {
+  if (cap <= 0 || tile_rows <= 0) return 0;
+  return (cap + tile_rows - 1) / tile_rows;
+}
+
+#if defined(__HIPCC__)
+#define MX_ROWS_HD __host__ __device__
+#else
+#define MX_ROWS_HD
+#endif
+
+// First index j in [0, n) of the ascending list with rows[j] >= v (n when there is none): the
+// listed-rows activation pass finds a block's range [lower_bound(r0), lower_bound(r1)) with it.
+MX_ROWS_HD inline int64_t rpn_rows_lower_bound(const int32_t* rows, int64_t n, int64_t v) {
+  int64_t lo = 0, hi = n > 0 ? n : 0;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if ((int64_t)rows[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
 }  // namespace mx

@@ -53,10 +53,9 @@ __global__ void __launch_bounds__(256) rpn_rows_dilate_kernel(const uint64_t* __
 // TILES: the entries are the 32-pixel groups (bitmap half-words) with any bit set, index p / 32.
 static constexpr int COMPACT_T = 1024;
 template <bool TILES>
-__global__ void __launch_bounds__(COMPACT_T) rpn_rows_compact_kernel(const uint64_t* __restrict__ bitmap, int64_t nwords,
-                                                                      int32_t* __restrict__ rows, int64_t cap,
-                                                                      int32_t* __restrict__ count,
-                                                                      int32_t* __restrict__ flag) {
+__device__ __forceinline__ void rpn_rows_compact_body(const uint64_t* __restrict__ bitmap, int64_t nwords,
+                                                      int32_t* __restrict__ rows, int64_t cap,
+                                                      int32_t* __restrict__ count, int32_t* __restrict__ flag) {
   __shared__ int wsum[COMPACT_T / 64];
   __shared__ int carry_s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -95,6 +94,25 @@ __global__ void __launch_bounds__(COMPACT_T) rpn_rows_compact_kernel(const uint6
     *count = total;
     if (total > cap) *flag = 1;
   }
+}
+
+template <bool TILES>
+__global__ void __launch_bounds__(COMPACT_T) rpn_rows_compact_kernel(const uint64_t* __restrict__ bitmap, int64_t nwords,
+                                                                      int32_t* __restrict__ rows, int64_t cap,
+                                                                      int32_t* __restrict__ count,
+                                                                      int32_t* __restrict__ flag) {
+  rpn_rows_compact_body<TILES>(bitmap, nwords, rows, cap, count, flag);
+}
+
+// Both forms of one bitmap in one launch: block 0 the pixel list, block 1 (when launched) the K-step list.
+__global__ void __launch_bounds__(COMPACT_T) rpn_rows_compact_both_kernel(const uint64_t* __restrict__ bitmap, int64_t nwords,
+                                                                           int32_t* __restrict__ rows, int64_t cap,
+                                                                           int32_t* __restrict__ count,
+                                                                           int32_t* __restrict__ tiles, int64_t tcap,
+                                                                           int32_t* __restrict__ tcount,
+                                                                           int32_t* __restrict__ flag) {
+  if (blockIdx.x == 0) rpn_rows_compact_body<false>(bitmap, nwords, rows, cap, count, flag);
+  else rpn_rows_compact_body<true>(bitmap, nwords, tiles, tcap, tcount, flag);
 }
 
 }  // namespace mx
@@ -151,4 +169,45 @@ extern "C" int mx_rpn_tiles_build(const float* g, int64_t N, int64_t H, int64_t 
                                   int32_t* counts, int32_t* flag, void* ws, size_t ws_bytes, mx_stream_t stream) {
   return rows_build<true>(g, N, H, W, C, levels, tiles0, cap0, tiles1, cap1, tiles2, cap2, counts, flag, ws, ws_bytes,
                           stream);
+}
+
+// One mark, two dilations, and both forms compacted from the same three bitmaps: the pixel lists S0..S2
+// (rows form of the dgrads and activation passes) and the K-step lists S0, S1 (tile-list wgrads).
+extern "C" int mx_rpn_lists_build(const float* g, int64_t N, int64_t H, int64_t W, int64_t C, int32_t* rows0, int64_t cap0,
+                                  int32_t* rows1, int64_t cap1, int32_t* rows2, int64_t cap2, int32_t* counts,
+                                  int32_t* tiles0, int64_t tcap0, int32_t* tiles1, int64_t tcap1, int32_t* tcounts,
+                                  int32_t* flag, void* ws, size_t ws_bytes, mx_stream_t stream) {
+  MX_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && C >= 1 && C < (1 << 16), "rpn lists: bad sizes");
+  MX_CHECK_ARG(H < (1 << 20) && W < (1 << 20) && N * H * W < (1ll << 31) - 64,
+               "rpn lists: map too large for 32-bit pixel indices");
+  MX_CHECK_ARG(g && counts && tcounts && flag && ws, "rpn lists: null argument");
+  const int64_t P = N * H * W;
+  MX_CHECK_ARG(ws_bytes >= rpn_rows_workspace(P), "rpn lists: workspace of %zu bytes required", rpn_rows_workspace(P));
+  int32_t* const rows[RPN_ROWS_LEVELS] = {rows0, rows1, rows2};
+  const int64_t caps[RPN_ROWS_LEVELS] = {cap0, cap1, cap2};
+  int32_t* const tiles[2] = {tiles0, tiles1};
+  const int64_t tcaps[2] = {tcap0, tcap1};
+  for (int l = 0; l < RPN_ROWS_LEVELS; ++l)
+    MX_CHECK_ARG(rows[l] && caps[l] >= 0 && caps[l] <= P, "rpn lists: pixel list %d needs a buffer and a capacity in [0, P]", l);
+  for (int l = 0; l < 2; ++l)
+    MX_CHECK_ARG(tiles[l] && tcaps[l] >= 0 && tcaps[l] <= rpn_tiles_total(P),
+                 "rpn lists: K-step list %d needs a buffer and a capacity in [0, ceil(P / 32)]", l);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nwords = rpn_rows_words(P);
+  uint64_t* bm[2] = {(uint64_t*)ws, (uint64_t*)((char*)ws + rpn_rows_workspace(P) / 2)};
+  const unsigned blocks = (unsigned)cdiv(P, 256);
+  rpn_rows_mark_kernel<<<blocks, 256, 0, st>>>((const uint32_t*)(const void*)g, P, (int)C, bm[0]);
+  MX_LAUNCH_CHECK();
+  for (int l = 0; l < RPN_ROWS_LEVELS; ++l) {
+    if (l > 0) {
+      rpn_rows_dilate_kernel<<<blocks, 256, 0, st>>>(bm[(l - 1) & 1], P, (int)H, (int)W, bm[l & 1]);
+      MX_LAUNCH_CHECK();
+    }
+    const bool both = l < 2;
+    rpn_rows_compact_both_kernel<<<both ? 2 : 1, COMPACT_T, 0, st>>>(bm[l & 1], nwords, rows[l], caps[l], counts + l,
+                                                                     both ? tiles[l] : nullptr, both ? tcaps[l] : 0,
+                                                                     both ? tcounts + l : nullptr, flag);
+    MX_LAUNCH_CHECK();
+  }
+  return MX_OK;
 }

@@ -245,6 +245,13 @@ _SIGS = {
                                    c_vp, c_vp, c_sz, c_vp]),
     "mx_conv2d_wgrad_x3_rows": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp,
                                         c_i64, c_vp, c_sz, c_vp, c_cfg]),
+    "mx_rpn_lists_build": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                   c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "mx_conv2d_dgrad_x3_rows_supported": (c_int, [ctypes.POINTER(ConvShape), c_cfg]),
+    "mx_conv2d_dgrad_x3_rows": (c_int, [ctypes.POINTER(ConvShape), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                        c_cfg]),
+    "mx_act_bias_bwd_rows": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_sz,
+                                     c_vp]),
     "mx_coco_match": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp,
                               c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mx_coco_accumulate_workspace": (c_sz, [c_i64]),

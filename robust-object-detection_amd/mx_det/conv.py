@@ -441,18 +441,55 @@ def _is_dense(x_shape, R, S, stride, pad):
     return (x_shape[1], x_shape[2]) == (R, S) and tuple(pad) == (0, 0) and R * S > 1
 
 
-def conv_dgrad(dy, wt, x_shape, R, S, stride, pad, residual=None, bnb=None):
+def conv_dgrad(dy, wt, x_shape, R, S, stride, pad, residual=None, bnb=None, rows=None, rows_fill=True,
+               rows_inplace=False):
     """dy NHWC [N,Ho,Wo,K] (K = the wt's padded output channels), wt from pack_weight(dgrad=True)
     -> dx NHWC [N,H,W,C] of dy's dtype (+ residual, a tensor of dx's shape and dtype added in the
-    epilogue, at every pixel once under either stride). f32 dy: bf16x3 kernels on the split wt."""
+    epilogue, at every pixel once under either stride). f32 dy: bf16x3 kernels on the split wt.
+
+    rows: (pixel list, count, capacity) of RowLists.pixels -- dx is nonzero only on the listed pixels
+    (dy zero wherever the dense gradient is): the rows form of the dense launch this shape would get (its
+    tuned cfg, kernel instance and sums: the same bits) computes those rows alone. The other rows of the
+    result are the residual's, or zero (rows_fill), or -- rows_fill=False, for a consumer that reads
+    listed rows only -- not written at all. rows_inplace: the residual buffer itself takes the rows and
+    is returned. A dense pick without a rows form (split K, another tile family) runs densely."""
     N, H, W, C = x_shape
     K = dy.shape[3]
     x3 = is_x3(dy)
     assert wt.numel() == (2 if x3 else 1) * C * R * S * K, (wt.numel(), C, R, S, K)
     Ho, Wo = out_hw(H, W, R, S, stride, pad)
     sh = _lib.ConvShape(N, H, W, C, K, R, S, Ho, Wo, stride[0], stride[1], pad[0], pad[1])
-    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
     dyc = dy.contiguous()
+    if rows is not None and x3 and bnb is None:
+        if residual is not None:
+            assert residual.dtype == dy.dtype and residual.shape == (N, H, W, C) and residual.is_contiguous()
+        key = ("dgrad", dy.dtype, N, H, W, C, K, R, S, tuple(stride), tuple(pad), residual is not None, False)
+        c = None
+        if _tune_on():
+            def trial(c_):  # the dense launch: the rows form follows its pick
+                cfg_ = _fd_cfg(c_)
+                wsb_ = _lib.load().mx_conv_workspace_x3(ctypes.byref(sh), 1, cfg_)
+                ws_ = torch.empty(wsb_, dtype=torch.uint8, device=dy.device) if wsb_ else None
+                tmp = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+                call("mx_conv2d_dgrad_x3", ctypes.byref(sh), _p(dyc), _p(wt), _p(residual), _p(tmp), None, None, None,
+                     None, 0, None, 0, _p(ws_), wsb_, _s(), cfg_)
+            c = _pick(key, _FD_CANDS_X3, trial)
+        cfg = _fd_cfg(c)
+        if _lib.load().mx_conv2d_dgrad_x3_rows_supported(ctypes.byref(sh), cfg):
+            t0 = _timer.start() if _timer else None
+            if residual is not None:
+                dx = residual if rows_inplace else residual.clone()
+            elif rows_fill:
+                dx = torch.zeros((N, H, W, C), dtype=dy.dtype, device=dy.device)
+            else:
+                dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+            call("mx_conv2d_dgrad_x3_rows", ctypes.byref(sh), _p(dyc), _p(wt), _p(dx) if residual is not None else None,
+                 _p(dx), _p(rows[0]), _p(rows[1]), rows[2], _s(), cfg)
+            if _timer:
+                _timer.stop("x3_dgrad", 2.0 * rows[2] * K * R * S * C, t0, _tag(N, H, W, C, K, R, S, stride),
+                            dy.numel() * dy.element_size() + wt.numel() * 2 + rows[2] * C * 4)
+            return dx
+    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
     t0 = _timer.start() if _timer else None
     if residual is not None:
         assert residual.dtype == dy.dtype and residual.shape == dx.shape and residual.is_contiguous()
@@ -730,6 +767,29 @@ def act_bias_bwd(gy, y, act, K8, need_db, g_dtype=torch.bfloat16):
     return g, db
 
 
+def act_bias_bwd_rows(gy, y, need_db, rows, mask=None):
+    """act_bias_bwd for ReLU on f32 maps whose gradient gy is nonzero only on the listed pixels (rows:
+    (pixel list, count, capacity) of RowLists.pixels): g's listed rows and db are the dense launch's
+    values (mx_act_bias_bwd_rows), every other row of g is an exact zero from ONE fill of the map --
+    the tile-list wgrad and the next dgrad's 3x3 gather read g beside the listed rows. Rows of gy off
+    the list are never read (they may be unwritten memory). mask: a [1,H,W,1] factor of gy, applied
+    first (the canvas frame mask's backward)."""
+    K = gy.shape[-1]
+    gy = gy.contiguous()
+    M = gy.numel() // K
+    assert gy.dtype == torch.float32 and y.dtype == gy.dtype and y.shape == gy.shape and K % 8 == 0
+    g = torch.zeros(gy.shape, dtype=gy.dtype, device=gy.device)
+    db = torch.empty(K, dtype=torch.float32, device=gy.device) if need_db else None
+    ws = bn_scratch(_lib.load().mx_act_bias_bwd_workspace(M, K), gy.device) if need_db else None
+    period = 0
+    if mask is not None:
+        assert mask.dtype == gy.dtype and mask.is_contiguous() and mask.numel() == gy.shape[1] * gy.shape[2], mask.shape
+        period = mask.numel()
+    call("mx_act_bias_bwd_rows", _p(gy), _p(y.contiguous()), _p(mask), period, M, K, _p(rows[0]), _p(rows[1]), rows[2],
+         _p(g), _p(db), _p(ws), ws.numel() if ws is not None else 0, _s())
+    return g, db
+
+
 class GradSlot:
     """Root-gradient absorption inside a captured backward graph: a graph output whose gradient arrives
     in a static buffer (frcnn._Graphs' static_gout) and whose only in-graph consumer can add it itself
@@ -882,7 +942,8 @@ class ConvAct(torch.autograd.Function):
         K, _, R, S = wshape
         dx = dw = db = None
         K8 = (K + 7) // 8 * 8
-        rows = None
+        rows = px_in = px_out = None
+        last = False
         if ctx.rows is not None:
             lists, role = ctx.rows
             if role == "src":  # the head's 1x1 conv: its gradient is the raw map's, nonzero on S0
@@ -890,7 +951,17 @@ class ConvAct(torch.autograd.Function):
                 rows = lists.level(0, gy)
             else:              # a tower conv: its output gradient is zero outside S<role>
                 rows = lists.level(role, gy)
-        gk, db = act_bias_bwd(gy, y, act, K8, has_b and ctx.needs_input_grad[2], g_dtype=x.dtype)
+                if lists.sparse:  # ... and is read on the pixel list only; its input gradient lives on S<role+1>
+                    if not (act == ACT_RELU and K8 == K and gy.dtype == torch.float32 and tuple(stride) == (1, 1)
+                            and not _is_dense(x.shape, R, S, stride, pad)):
+                        raise RuntimeError("RowLists: a tower conv of the row-sparse RPN head backward must be a "
+                                           "stride-1 f32 ReLU conv with a multiple of 8 output channels")
+                    px_in, px_out = lists.pixels(role, gy), lists.pixels(role + 1, gy)
+                    last = role == lists.top
+        if px_in is not None:
+            gk, db = act_bias_bwd_rows(gy, y, has_b and ctx.needs_input_grad[2], px_in, lists.take_mask(role))
+        else:
+            gk, db = act_bias_bwd(gy, y, act, K8, has_b and ctx.needs_input_grad[2], g_dtype=x.dtype)
         wg = _wgrad_plan(ctx, gk, x, K8, R, S, stride, pad, kout=K, cin=wshape[1], rows=rows)  # before the dgrad
         if ctx.needs_input_grad[0]:
             if _is_dense(x.shape, R, S, stride, pad):  # 1x1-GEMM form: dX[N, R*S*C] = dY[N, K8] wt
@@ -905,7 +976,12 @@ class ConvAct(torch.autograd.Function):
                 if extra is not None and not (extra.dtype == gk.dtype and extra.shape == x.shape and
                                               extra.is_contiguous()):
                     raise RuntimeError("absorbed gradient needs an input-shaped buffer of the gradient's dtype")
-                dx = conv_dgrad(gk, wt, x.shape, R, S, stride, pad, residual=_chain_res(ctx.chain, extra))
+                res = _chain_res(ctx.chain, extra)
+                # row-sparse head: the last tower dgrad feeds dense consumers (its rows are added into a
+                # claimed slot's buffer in place, else scattered over one fill); an earlier one is read
+                # by the next conv's listed-rows pass only and needs no fill
+                dx = conv_dgrad(gk, wt, x.shape, R, S, stride, pad, residual=res, rows=px_out, rows_fill=last,
+                                rows_inplace=res is not None and res is extra)
             if ctx.chain is not None:
                 dx = ctx.chain.hand(dx)
         if wg is not None:
@@ -926,12 +1002,32 @@ class RowLists:
     nb = N * batch_size_per_image bounds S0 (RegionProposalNetwork hands it to its head); a gradient
     with more nonzero pixels -- a dense one: the graph captures' ones_like warm-ups -- overflows: the
     lists are cut at their capacities, the device flag is set, and rows_check() raises at the step's
-    next host check unless rows_reset() cleared it (after a capture)."""
+    next host check unless rows_reset() cleared it (after a capture).
+
+    sparse=True (MX_RPN_SPARSE_BWD other than "wgrad" / "0") adds the pixel lists S0, S1, S2 from the same
+    bitmaps (mx_rpn_lists_build): the tower convs' ReLU / bias passes and dgrads then visit listed
+    pixels only, with the dense launches' sums (act_bias_bwd_rows, conv_dgrad rows=)."""
     LEVELS = 2
 
-    def __init__(self, nb):
+    def __init__(self, nb, sparse=False, top=LEVELS - 1):
+        """sparse: also the pixel lists S0, S1, S2 (mx_rpn_lists_build builds both forms from one set of
+        bitmaps) -- the tower convs' activation passes and dgrads then run on listed pixels only
+        (act_bias_bwd_rows, conv_dgrad rows=): a tower conv of role r reads its output gradient on S<r>
+        and writes its input gradient on S<r+1>; `top` is the role of the first tower conv, whose input
+        gradient leaves the head for dense consumers. A [1,H,W,1] factor between two tower convs (the
+        canvas frame mask, MaskMul) is handed to the upstream conv's pass by role."""
         self.nb = int(nb)
         self.lists = None
+        self.sparse = bool(sparse)
+        self.top = int(top)
+        self.masks = {}
+        self.px = None
+
+    def set_mask(self, role, mask):
+        self.masks[role] = mask
+
+    def take_mask(self, role):
+        return self.masks.pop(role, None)
 
     def build(self, gy):
         assert gy.dtype == torch.float32 and gy.dim() == 4, (gy.dtype, gy.shape)
@@ -939,6 +1035,9 @@ class RowLists:
         N, H, W, C = gy.shape
         P = N * H * W
         lib = _lib.load()
+        if self.sparse:
+            return self._build_both(gy, lib)
+        self.px = None
         caps = [lib.mx_rpn_tiles_capacity(P, self.nb, l) for l in range(self.LEVELS)]
         flag = _rows_flag(gy.device)
         buf = torch.empty(sum(caps) + 4, dtype=torch.int32, device=gy.device)
@@ -956,6 +1055,35 @@ class RowLists:
                                                       enumerate(zip(rows, caps))], buf)
         _rows_watch(gy.device)
 
+    def _build_both(self, gy, lib):
+        N, H, W, C = gy.shape
+        P = N * H * W
+        caps = [lib.mx_rpn_rows_capacity(P, self.nb, l) for l in range(3)]
+        tcaps = [lib.mx_rpn_tiles_capacity(P, self.nb, l) for l in range(self.LEVELS)]
+        flag = _rows_flag(gy.device)
+        buf = torch.empty(sum(caps) + sum(tcaps) + 8, dtype=torch.int32, device=gy.device)
+        parts, o = [], 0
+        for c in caps + tcaps:
+            parts.append(buf[o:o + c])
+            o += c
+        counts, tcounts = buf[o:o + 4], buf[o + 4:o + 8]
+        rows, tiles = parts[:3], parts[3:]
+        wsb = lib.mx_rpn_rows_workspace(P)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=gy.device)
+        call("mx_rpn_lists_build", _p(gy), N, H, W, C, _p(rows[0]), caps[0], _p(rows[1]), caps[1], _p(rows[2]), caps[2],
+             _p(counts), _p(tiles[0]), tcaps[0], _p(tiles[1]), tcaps[1], _p(tcounts), _p(flag), _p(ws), wsb, _s())
+        self.lists = (gy.shape[:3], _cur_stream(gy), [(r, tcounts[l:l + 1], c) for l, (r, c) in
+                                                      enumerate(zip(tiles, tcaps))], buf)
+        self.px = [(r, counts[l:l + 1], c) for l, (r, c) in enumerate(zip(rows, caps))]
+        _rows_watch(gy.device)
+
+    def pixels(self, l, gy):
+        """(pixel list, count, capacity) of S<l> (sparse lists only) for a conv of gy's map."""
+        self.level(min(l, self.LEVELS - 1), gy)  # the shape and stream checks
+        if self.px is None:
+            raise RuntimeError("RowLists: the pixel lists were not built (sparse=False)")
+        return self.px[l]
+
     def level(self, l, gy):
         """(K-step list, count, capacity) of S<l> for the conv whose output gradient is gy."""
         if self.lists is None:
@@ -965,6 +1093,26 @@ class RowLists:
             raise RuntimeError("RowLists: a tower conv's gradient has another map shape or stream than the "
                                "head conv's, whose lists it would walk")
         return lv[l]
+
+
+class MaskMul(torch.autograd.Function):
+    """t * mask for a constant [1,H,W,1] mask between two tower convs of a row-sparse head (the canvas
+    frame mask): the forward is the torch multiply; the backward hands the mask to the upstream conv's
+    listed-rows activation pass (RowLists.set_mask: g = (gy * mask) * act', the order of the torch
+    multiply followed by the pass) instead of a full-map multiply of a gradient that is read on the
+    listed rows only."""
+
+    @staticmethod
+    def forward(ctx, t, mask, lists, role):
+        ctx.mask, ctx.lists, ctx.role = mask, lists, role
+        return t * mask
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.lists.sparse:
+            ctx.lists.set_mask(ctx.role, ctx.mask.contiguous())
+            return g, None, None, None
+        return g * ctx.mask, None, None, None
 
 
 _rows_flags = {}

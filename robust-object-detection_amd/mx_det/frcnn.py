@@ -254,22 +254,34 @@ class RPNHead(nn.Module):
         batch_size_per_image anchors per image, so the tower convs' weight gradients visit only the
         pixels the raw map's gradient can have spread to. A head used on its own stays dense."""
         B = self.__dict__.get("sparse_rows_per_image")
+        mode = os.environ.get("MX_RPN_SPARSE_BWD", "1")
         if (B is None or not t.is_cuda or getattr(be, "name", "") != "hip" or t.dtype != torch.float32
-                or not torch.is_grad_enabled() or t.shape[3] % 8 or os.environ.get("MX_RPN_SPARSE_BWD", "1") == "0"):
+                or not torch.is_grad_enabled() or t.shape[3] % 8 or mode == "0"):
             return None
-        return mc.RowLists(t.shape[0] * B)
+        # "wgrad": the tile-list weight gradients alone; anything else: the listed-rows activation
+        # passes and dgrads too (3x3 stride-1 ReLU tower convs: what the rows forms cover)
+        tower = all(not c.norm and tuple(c[0].weight.shape[2:]) == (3, 3) and c[0].stride == (1, 1)
+                    and c[0].padding == (1, 1) and c[0].act == ACT_RELU and c[0].weight.shape[0] % 8 == 0
+                    for c in self.conv)
+        return mc.RowLists(t.shape[0] * B, sparse=mode != "wgrad" and tower and len(self.conv) >= 1,
+                           top=min(len(self.conv), mc.RowLists.LEVELS) - 1)
 
     def _run(self, t, be, w, b, mask=None):
         lists = self._row_lists(t, be)
         n = len(self.conv)
         for ci, c in enumerate(self.conv):
             # the last tower conv's output gradient lives on S0, the one before it on S1 (conv.RowLists)
-            if lists is not None and n - 1 - ci < mc.RowLists.LEVELS:
-                t = c(t, be, rows=(lists, n - 1 - ci))
+            role = n - 1 - ci
+            if lists is not None and role < mc.RowLists.LEVELS:
+                t = c(t, be, rows=(lists, role))
             else:
                 t = c(t, be)
             if mask is not None and ci + 1 < n:
-                t = t * mask  # zero frame between levels: the next 3x3 conv reads it as padding
+                # zero frame between levels: the next 3x3 conv reads it as padding
+                if lists is not None and lists.sparse and role <= lists.top:
+                    t = mc.MaskMul.apply(t, mask, lists, role)
+                else:
+                    t = t * mask
         if lists is not None:
             return be.conv(t, w, b, (1, 1), (0, 0), ACT_NONE, out_dtype=torch.float32, rows=(lists, "src"))
         return be.conv(t, w, b, (1, 1), (0, 0), ACT_NONE, out_dtype=torch.float32)  # [N,H,W,A*5]
