@@ -744,6 +744,29 @@ int mx_bn_finalize_ex(const float* stats, int64_t mblocks, int64_t K, int64_t co
                       const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                       float* mean_out, float* invstd_out, float* scale_out, float* shift_out, void* ws,
                       size_t ws_bytes, mx_stream_t stream);
+/* Test-time BatchNorm adaptation for the eval forward (prediction-time BN, Nado et al. 2020; the blend
+ * with a source prior is Schneider et al. 2020, eq. 1). The reference evaluates with the running
+ * statistics only (evaluate_frcnn.py, model.eval()); this is an opt-in addition. One launch with the
+ * grid, workspace (mx_bn_finalize_workspace(mblocks, K)) and zero-kept counters of mx_bn_finalize_ex.
+ * Per channel, in f64, from the partials of this forward's `count` rows:
+ *   m_b = sum z / count,  v_b = max(sum z^2 / count - m_b^2, 0)                  (biased variance)
+ *   state null (batch mode): (m_t, v_t) = (m_b, v_b)
+ *   state [3][K] f64 = (rows, mean, M2), zero at the start (stream mode), merged in place (Chan):
+ *     d = m_b - mean, rows' = rows + count, mean' = mean + d*count/rows',
+ *     M2' = M2 + v_b*count + d^2*rows*count/rows',  (m_t, v_t) = (mean', M2'/rows')
+ *   a = prior / (prior + n_images),  mu = a*src_mean + (1-a)*m_t,  var = a*src_var + (1-a)*v_t
+ *   mean_out = (float)mu, var_out = (float)var, invstd = (float)(1/sqrt(var + eps)),
+ *   scale_out = gamma*invstd, shift_out = beta - (float)mu*scale_out     (as mx_bn_finalize_ex)
+ * prior and n_images count images; n_images is the number of images behind (m_t, v_t), this forward
+ * included (the caller keeps it: nothing is read back). gamma / beta nullable (1 / 0). src_mean and
+ * src_var (the module's running statistics) are read only; no running statistic is written. Errors
+ * (outputs untouched): prior < 0, prior + n_images <= 0, null src_mean / src_var, K > 4096, a short
+ * workspace. */
+int mx_bn_finalize_adapt(const float* stats, int64_t mblocks, int64_t K, int64_t count, const float* gamma,
+                         const float* beta, float eps, const float* src_mean, const float* src_var, double prior,
+                         double n_images, double* state /* nullable; [3][K] rows, mean, M2; updated in place */,
+                         float* mean_out, float* var_out, float* scale_out, float* shift_out, void* ws, size_t ws_bytes,
+                         mx_stream_t stream);
 /* apply: x of xdtype, residual and y of ydtype (bf16 -> bf16, f32 -> bf16, f32 -> f32). */
 int mx_bn_apply(const void* x, int xdtype, int64_t M, int64_t K, const float* scale, const float* shift,
                 const void* residual, int act, void* y, int ydtype, mx_stream_t stream);

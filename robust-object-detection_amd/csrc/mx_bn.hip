@@ -85,13 +85,12 @@ __device__ __forceinline__ void last_sums(const T* __restrict__ part, int64_t R,
   __syncthreads();
 }
 
-// finalize: grid (channel chunks of 64, RS row slices); block = 64 channels x 4 row lanes (one wave
-// per row: 256-B coalesced reads of the [2][mb][K] conv-epilogue partials), f64 accumulation.
-__global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restrict__ stats, int64_t mb, int64_t K, int64_t count,
-                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float mom,
-                                   float* __restrict__ rmean, float* __restrict__ rvar, float* __restrict__ mean_o,
-                                   float* __restrict__ invstd_o, float* __restrict__ scale_o, float* __restrict__ shift_o,
-                                   unsigned* __restrict__ ctr, double* __restrict__ part) {
+// The shared front of the finalize kernels: grid (channel chunks of 64, RS row slices); block = 64
+// channels x 4 row lanes (one wave per row: 256-B coalesced reads of the [2][mb][K] partials), f64
+// accumulation. Every block stores its slice's two column sums; true only in the last block to
+// arrive for its chunk, with fin[w][col] = the column sums over all mb rows of plane w.
+__device__ __forceinline__ bool fin_front(const float* __restrict__ stats, int64_t mb, int64_t K,
+                                          unsigned* __restrict__ ctr, double* __restrict__ part, double (*fin)[64]) {
   __shared__ double red[2][4][64];
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int64_t k = (int64_t)blockIdx.x * 64 + cl;
@@ -118,25 +117,91 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restric
     const double v = (red[rl][0][cl] + red[rl][1][cl]) + (red[rl][2][cl] + red[rl][3][cl]);
     st_sc1(part + ((int64_t)rl * RS + blockIdx.y) * K + k, v);
   }
-  if (!arrive_last(ctr + blockIdx.x, (unsigned)RS)) return;
-  __shared__ double fin[2][64], scr[256];
+  if (!arrive_last(ctr + blockIdx.x, (unsigned)RS)) return false;
+  __shared__ double scr[256];
   last_sums<2>(part, RS, K, (int64_t)blockIdx.x * 64, fin, scr);
+  return true;
+}
+
+// Batch statistics of one channel from its column sums (biased variance, clamped at 0), and the
+// apply's coefficients from a mean / variance pair: shared by the train-mode and the adaptive finalize,
+// so both round alike.
+__device__ __forceinline__ void batch_stats(double s, double q, int64_t count, double& mean, double& var) {
+  mean = s / (double)count;
+  var = q / (double)count - mean * mean;
+  if (var < 0.0) var = 0.0;
+}
+__device__ __forceinline__ float affine_out(double mean, double var, float eps, const float* __restrict__ gamma,
+                                            const float* __restrict__ beta, int64_t k, float* __restrict__ scale_o,
+                                            float* __restrict__ shift_o) {
+  const float invstd = (float)(1.0 / sqrt(var + (double)eps));
+  const float g = gamma ? gamma[k] : 1.f, bb = beta ? beta[k] : 0.f;
+  scale_o[k] = g * invstd;
+  shift_o[k] = bb - (float)mean * (g * invstd);
+  return invstd;
+}
+
+// finalize: fin_front, then the last block of each chunk writes its channels.
+__global__ void __launch_bounds__(256) bn_finalize_kernel(const float* __restrict__ stats, int64_t mb, int64_t K, int64_t count,
+                                   const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float mom,
+                                   float* __restrict__ rmean, float* __restrict__ rvar, float* __restrict__ mean_o,
+                                   float* __restrict__ invstd_o, float* __restrict__ scale_o, float* __restrict__ shift_o,
+                                   unsigned* __restrict__ ctr, double* __restrict__ part) {
+  __shared__ double fin[2][64];
+  if (!fin_front(stats, mb, K, ctr, part, fin)) return;
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int64_t k = (int64_t)blockIdx.x * 64 + cl;
   if (rl == 0 && k < K) {
-    const double s = fin[0][cl], q = fin[1][cl];
-    const double mean = s / (double)count;
-    double var = q / (double)count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float g = gamma ? gamma[k] : 1.f, bb = beta ? beta[k] : 0.f;
+    double mean, var;
+    batch_stats(fin[0][cl], fin[1][cl], count, mean, var);
     mean_o[k] = (float)mean;
-    invstd_o[k] = invstd;
-    scale_o[k] = g * invstd;
-    shift_o[k] = bb - (float)mean * (g * invstd);
+    invstd_o[k] = affine_out(mean, var, eps, gamma, beta, k, scale_o, shift_o);
     if (rmean) {
       const double unb = count > 1 ? var * (double)count / (double)(count - 1) : var;
       rmean[k] = (float)((1.0 - mom) * rmean[k] + mom * mean);
       rvar[k] = (float)((1.0 - mom) * rvar[k] + mom * unb);
     }
+  }
+}
+
+// Test-time adaptation (prediction-time BN, Nado et al. 2020, with the source prior of Schneider et
+// al. 2020, eq. 1): the front of bn_finalize_kernel, then per channel in f64 the batch statistics,
+// the merge into the layer's running target statistics (state [3][K] = rows, mean, M2; Chan's
+// formula; null: the batch alone), and the blend with the source statistics, a = prior / (prior + n)
+// counted in images. The last block of a chunk reads and writes only its own channels of the state,
+// with ordinary stores: the next launch on the stream is ordered behind them.
+__global__ void __launch_bounds__(256) bn_finalize_adapt_kernel(const float* __restrict__ stats, int64_t mb, int64_t K, int64_t count,
+                                         const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                         const float* __restrict__ smean, const float* __restrict__ svar, double prior,
+                                         double n_images, double* __restrict__ state, float* __restrict__ mean_o,
+                                         float* __restrict__ var_o, float* __restrict__ scale_o,
+                                         float* __restrict__ shift_o, unsigned* __restrict__ ctr,
+                                         double* __restrict__ part) {
+  __shared__ double fin[2][64];
+  if (!fin_front(stats, mb, K, ctr, part, fin)) return;
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int64_t k = (int64_t)blockIdx.x * 64 + cl;
+  if (rl == 0 && k < K) {
+    double mt, vt;
+    batch_stats(fin[0][cl], fin[1][cl], count, mt, vt);
+    if (state) {
+      const double c = (double)count, rows = state[k], m0 = state[K + k], M2 = state[2 * K + k];
+      const double d = mt - m0, rows1 = rows + c;
+      const double w = c / rows1;  // 1 on an empty state: the first merge stores the batch mean itself
+      const double m1 = m0 + d * w;
+      const double M21 = M2 + vt * c + d * d * rows * w;
+      state[k] = rows1;
+      state[K + k] = m1;
+      state[2 * K + k] = M21;
+      mt = m1;
+      vt = M21 / rows1;
+    }
+    const double a = prior / (prior + n_images);
+    const double mu = a * (double)smean[k] + (1.0 - a) * mt;
+    const double var = a * (double)svar[k] + (1.0 - a) * vt;
+    mean_o[k] = (float)mu;
+    var_o[k] = (float)var;
+    affine_out(mu, var, eps, gamma, beta, k, scale_o, shift_o);
   }
 }
 
@@ -149,35 +214,10 @@ __global__ void __launch_bounds__(256) bn_bwd_finalize_kernel(const float* __res
                                                               const float* __restrict__ gamma, float* __restrict__ sums,
                                                               float* __restrict__ coef, unsigned* __restrict__ ctr,
                                                               double* __restrict__ part) {
-  __shared__ double red[2][4][64];
+  __shared__ double fin[2][64];
+  if (!fin_front(stats, mb, K, ctr, part, fin)) return;
   const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int64_t k = (int64_t)blockIdx.x * 64 + cl;
-  const int64_t RS = gridDim.y, per = (mb + RS - 1) / RS;
-  const int64_t r0 = (int64_t)blockIdx.y * per, r1 = min<int64_t>(mb, r0 + per);
-  double s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
-  if (k < K) {
-    int64_t r = r0 + rl;
-    for (; r + 4 < r1; r += 8) {
-      s0 += (double)stats[r * K + k];
-      q0 += (double)stats[(mb + r) * K + k];
-      s1 += (double)stats[(r + 4) * K + k];
-      q1 += (double)stats[(mb + r + 4) * K + k];
-    }
-    if (r < r1) {
-      s0 += (double)stats[r * K + k];
-      q0 += (double)stats[(mb + r) * K + k];
-    }
-  }
-  red[0][rl][cl] = s0 + s1;
-  red[1][rl][cl] = q0 + q1;
-  __syncthreads();
-  if (rl < 2 && k < K) {
-    const double v = (red[rl][0][cl] + red[rl][1][cl]) + (red[rl][2][cl] + red[rl][3][cl]);
-    st_sc1(part + ((int64_t)rl * RS + blockIdx.y) * K + k, v);
-  }
-  if (!arrive_last(ctr + blockIdx.x, (unsigned)RS)) return;
-  __shared__ double fin[2][64], scr[256];
-  last_sums<2>(part, RS, K, (int64_t)blockIdx.x * 64, fin, scr);
   if (rl == 0 && k < K) {
     const double sg = fin[0][cl], sgx = fin[1][cl];
     sums[k] = (float)sg;
@@ -720,6 +760,28 @@ extern "C" int mx_bn_finalize_ex(const float* stats, int64_t mb, int64_t K, int6
   bn_finalize_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(stats, mb, K, count, gamma, beta, eps, momentum, rm, rv, mean,
                                                             invstd, scale, shift, (unsigned*)ws,
                                                             (double*)((char*)ws + CTR_BYTES));
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+extern "C" int mx_bn_finalize_adapt(const float* stats, int64_t mb, int64_t K, int64_t count, const float* gamma,
+                                    const float* beta, float eps, const float* src_mean, const float* src_var,
+                                    double prior, double n_images, double* state, float* mean, float* var, float* scale,
+                                    float* shift, void* ws, size_t ws_bytes, mx_stream_t stream) {
+  MX_CHECK_ARG(mb > 0 && K > 0 && count > 0, "bn_finalize_adapt: bad sizes");
+  MX_CHECK_ARG(stats && mean && var && scale && shift, "bn_finalize_adapt: bad arguments");
+  MX_CHECK_ARG(src_mean && src_var, "bn_finalize_adapt: source mean / var required");
+  MX_CHECK_ARG(prior >= 0.0 && prior <= 1e300, "bn_finalize_adapt: prior < 0 (or not finite)");
+  MX_CHECK_ARG(n_images >= 0.0 && n_images <= 1e300 && prior + n_images > 0.0,
+               "bn_finalize_adapt: prior + n_images <= 0 (or n_images negative / not finite)");
+  MX_CHECK_ARG(cdiv(K, 64) <= MAX_CHUNKS, "bn_finalize_adapt: K > %d", MAX_CHUNKS * 64);
+  const size_t need = mx_bn_finalize_workspace(mb, K);
+  MX_CHECK_ARG(ws && ws_bytes >= need, "bn_finalize_adapt: workspace of %zu bytes required (mx_bn_finalize_workspace)",
+               need);
+  dim3 grid((unsigned)cdiv(K, 64), (unsigned)fin_slices(mb));
+  bn_finalize_adapt_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(stats, mb, K, count, gamma, beta, eps, src_mean, src_var,
+                                                                  prior, n_images, state, mean, var, scale, shift,
+                                                                  (unsigned*)ws, (double*)((char*)ws + CTR_BYTES));
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

@@ -87,6 +87,7 @@ def default_precision():
 class HipBackend:
     name = "hip"
     stem_channels = 8  # RGB padded to 8 channels for the 8-channel gather of the stem conv
+    bn_adapt = True  # conv_bn takes the test-time adaptation branch (mx_det.adapt.BNAdapter)
 
     def __init__(self, precision=None):
         self.precision = precision or default_precision()

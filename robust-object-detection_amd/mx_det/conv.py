@@ -1263,21 +1263,79 @@ def bn_train_finalize(st, K, M, gamma, beta, eps, momentum, rmean, rvar):
     return mean, invstd, scale, shift
 
 
-def conv_bn_act_maxpool(x, conv, bn, act, k, st, pd):
+def bn_adapting(bn):
+    """The module's test-time adaptation record (mx_det.adapt.BNAdapter marks the modules in its scope
+    in their __dict__, as count_batches does) when its adapter is enabled, else None."""
+    ad = bn.__dict__.get("_mx_adapt")
+    return ad if ad is not None and ad.owner.enabled else None
+
+
+def bn_adapt_finalize(st, K, M, images, bn, ad):
+    """Test-time BatchNorm statistics from the conv's partials st [2, mb, K] of `images` images
+    (mx_bn_finalize_adapt): the apply's scale / shift from the blend of the module's running statistics
+    with this forward's (batch mode) or with the merged statistics of every forward since the last
+    reset (stream mode: ad.state, ad.images). The blended mean / var stay in ad.mean / ad.var (what
+    freeze() keeps); the module's buffers are only read."""
+    scale = torch.empty(K, dtype=torch.float32, device=st.device)
+    shift = torch.empty_like(scale)
+    ad.prepare(K, st.device)
+    n = ad.count(images)
+    fws = bn_scratch(_lib.load().mx_bn_finalize_workspace(st.shape[1], K), st.device)
+    call("mx_bn_finalize_adapt", _p(st), st.shape[1], K, M, _p(bn.weight.detach()), _p(bn.bias.detach()), float(bn.eps),
+         _p(bn.running_mean), _p(bn.running_var), float(ad.owner.prior), float(n), _p(ad.state), _p(ad.mean),
+         _p(ad.var), _p(scale), _p(shift), _p(fws), fws.numel(), _s())
+    return scale, shift
+
+
+def _no_grad_inputs(x, conv, bn):
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("test-time BatchNorm adaptation has no backward: run it under torch.no_grad() "
+                           "(the input of an adapted conv + BatchNorm requires grad)")
+    if conv.bias is not None:
+        raise ValueError("test-time BatchNorm adaptation: the conv in front of an adapted BatchNorm has no bias")
+
+
+def adapt_conv_bn(x, conv, bn, act, residual, ad):
+    """conv_bn's eval forward under test-time adaptation: the conv with statistics, the adaptive
+    finalize and the apply (residual and activation as in ConvBNAct.forward); once frozen, the folded
+    eval conv with the adapter's statistics in place of the running ones."""
+    _no_grad_inputs(x, conv, bn)
+    if ad.frozen:
+        return eval_conv_bn(x, conv, bn, act, residual, ad.mean, ad.var)
+    w = conv.weight
+    wk, _ = operands(w, x.shape[3], conv.stride, conv.padding, _ceil8(w.shape[0]), False, split=is_x3(x))
+    z, st = conv_fwd(x.contiguous(), wk, conv.stride, conv.padding, stats=True, cin=w.shape[1])
+    K = w.shape[0]
+    M = z.numel() // K
+    scale, shift = bn_adapt_finalize(st, K, M, z.shape[0], bn, ad)
+    y = torch.empty_like(z)
+    res = residual.contiguous() if residual is not None else None
+    call("mx_bn_apply", _p(z), dcode(z), M, K, _p(scale), _p(shift), _p(res), int(act), _p(y), dcode(y), _s())
+    return y
+
+
+def conv_bn_act_maxpool(x, conv, bn, act, k, st, pd, adapt=None):
     """Forward-only conv -> train-mode BatchNorm -> act -> max pool, for a block no gradient flows
     through (the frozen ResNet stem: conv1 / bn1 parameters frozen, image input): the conv writes the
     BN statistics partials (mx_conv2d_stem_x3 for the 7x7 stem), and the BN apply runs inside the pool
     (mx_bn_act_maxpool), so the full-resolution activation is written once (the conv output) and
-    never re-written. Same running-stat update and result as conv_bn + maxpool."""
-    assert is_x3(x) and bn.training
-    if bn.num_batches_tracked is not None and not batch_counted(bn):
+    never re-written. Same running-stat update and result as conv_bn + maxpool. adapt: the module's
+    adaptation record (bn_adapting) in eval -- the same route with the adaptive finalize, which
+    writes no running statistic."""
+    assert is_x3(x) and (bn.training or adapt is not None)
+    if adapt is not None:
+        _no_grad_inputs(x, conv, bn)
+    elif bn.num_batches_tracked is not None and not batch_counted(bn):
         bn.num_batches_tracked.add_(1)
     w = conv.weight
     wk, _ = operands(w, x.shape[3], conv.stride, conv.padding, _ceil8(w.shape[0]), False, split=True)
     z, stt = conv_fwd(x.contiguous(), wk, conv.stride, conv.padding, stats=True, cin=w.shape[1])
     N, H, W, K = z.shape
-    _, _, scale, shift = bn_train_finalize(stt, K, N * H * W, bn.weight, bn.bias, bn.eps, bn.momentum,
-                                           bn.running_mean, bn.running_var)
+    if adapt is not None:
+        scale, shift = bn_adapt_finalize(stt, K, N * H * W, N, bn, adapt)
+    else:
+        _, _, scale, shift = bn_train_finalize(stt, K, N * H * W, bn.weight, bn.bias, bn.eps, bn.momentum,
+                                               bn.running_mean, bn.running_var)
     Ho, Wo = (H + 2 * pd - k) // st + 1, (W + 2 * pd - k) // st + 1
     y = torch.empty((N, Ho, Wo, K), dtype=torch.float32, device=z.device)
     call("mx_bn_act_maxpool", _p(z), N, H, W, K, _p(scale), _p(shift), int(act), k, st, pd, _p(y), _s())
@@ -1456,6 +1514,9 @@ def conv_bn(x, conv, bn, act, residual=None, link=None, bnb_own=None, bnb_feed=N
             bn.num_batches_tracked.add_(1)
         return ConvBNAct.apply(x, conv.weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
                                conv.stride, conv.padding, act, bn.eps, bn.momentum, link, bnb_own, bnb_feed)
+    ad = bn_adapting(bn)
+    if ad is not None:  # test-time adaptation (mx_det.adapt.BNAdapter): opt-in, eval only
+        return adapt_conv_bn(x, conv, bn, act, residual, ad)
     return eval_conv_bn(x, conv, bn, act, residual)
 
 
@@ -1484,18 +1545,21 @@ class ConvNormAct(torch.nn.Sequential):
         return be.conv(x, c.weight, c.bias, c.stride, c.padding, c.act, c.out_dtype)
 
 
-def fold_bn(conv, bn):
-    """Eval-mode BatchNorm folded into the conv: w' = w*gamma/sqrt(var+eps), b' = beta - mean*scale."""
-    scale = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
+def fold_bn(conv, bn, mean=None, var=None):
+    """Eval-mode BatchNorm folded into the conv: w' = w*gamma/sqrt(var+eps), b' = beta - mean*scale.
+    mean / var: statistics to fold in place of the module's running ones (a frozen BNAdapter's)."""
+    mean = bn.running_mean if mean is None else mean
+    var = bn.running_var if var is None else var
+    scale = bn.weight.detach() / torch.sqrt(var + bn.eps)
     w = conv.weight.detach() * scale.view(-1, 1, 1, 1)
-    b = bn.bias.detach() - bn.running_mean * scale
+    b = bn.bias.detach() - mean * scale
     if conv.bias is not None:
         b = b + conv.bias.detach() * scale
     return w, b.float().contiguous()
 
 
-def eval_conv_bn(x, conv, bn, act, residual=None):
-    w, b = fold_bn(conv, bn)
+def eval_conv_bn(x, conv, bn, act, residual=None, mean=None, var=None):
+    w, b = fold_bn(conv, bn, mean, var)
     wk, _ = pack_weight(w, x.shape[3], conv.stride, conv.padding, split=is_x3(x))
     return conv_fwd(x.contiguous(), wk, conv.stride, conv.padding, bias=b, residual=residual, act=act,
                     cin=conv.weight.shape[1])

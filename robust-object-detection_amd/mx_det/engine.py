@@ -371,9 +371,32 @@ def load_frcnn_checkpoint(ckpt_path, dev):
     return model.to(dev).eval()
 
 
-def eval_frcnn_variant(model, img_dir, ann_file, dev, restorer=None):
+class _FreezeAfter:
+    """Freezes a stream-mode BNAdapter once it has merged `images` images of the variant (checked
+    between batches: MX_BN_ADAPT_FREEZE_AFTER)."""
+
+    def __init__(self, loader, adapter, images):
+        self.loader, self.adapter, self.images = loader, adapter, int(images)
+        if self.images < 1:
+            raise ValueError(f"freeze_after must be at least 1 image, got {images!r}")
+
+    def __iter__(self):
+        for batch in self.loader:
+            if not self.adapter.frozen and self.adapter.images_seen >= self.images:
+                self.adapter.freeze()
+            yield batch
+
+    def __len__(self):
+        return len(self.loader)
+
+
+def eval_frcnn_variant(model, img_dir, ann_file, dev, restorer=None, adapter=None, freeze_after=None):
     """One test-set variant (eval_all.py:97-143). restorer: optional device U-Net applied to every
-    uint8 image before detection (the fused restored-eval path of eval_restored.py)."""
+    uint8 image before detection (the fused restored-eval path of eval_restored.py). adapter: an
+    mx_det.adapt.BNAdapter of `model` -- reset at the start (every variant is its own domain), enabled
+    for the loop and disabled after it; freeze_after (stream mode; default MX_BN_ADAPT_FREEZE_AFTER,
+    unset: never) freezes it after that many images of the variant. With world > 1 each rank adapts on
+    its own shard."""
     from .dataset import COCODetectionDataset, collate_fn, uint8_transform
     world, rank, _ = dist_info()
     device_jpeg = os.environ.get("MX_DEVICE_JPEG", "1") != "0"
@@ -385,7 +408,18 @@ def eval_frcnn_variant(model, img_dir, ann_file, dev, restorer=None):
         loader = DeviceJpegLoader(loader, dev)
     if restorer is not None:
         loader = _RestoredLoader(loader, restorer, dev)
-    return evaluate(model, loader, ann_file, dev, per_class=True)
+    if adapter is None:
+        return evaluate(model, loader, ann_file, dev, per_class=True)
+    if freeze_after is None and os.environ.get("MX_BN_ADAPT_FREEZE_AFTER"):
+        freeze_after = int(os.environ["MX_BN_ADAPT_FREEZE_AFTER"])
+    if freeze_after is not None and adapter.mode == "stream":
+        loader = _FreezeAfter(loader, adapter, freeze_after)
+    adapter.reset()
+    adapter.enable()
+    try:
+        return evaluate(model, loader, ann_file, dev, per_class=True)
+    finally:
+        adapter.disable()
 
 
 class DeviceJpegLoader:

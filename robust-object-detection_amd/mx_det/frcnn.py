@@ -108,6 +108,11 @@ class ResNet50Body(nn.Module):
             # frozen stem (torchvision trainable_layers <= 4): no gradient flows through conv1 / bn1 /
             # relu / maxpool, so the BN apply runs inside the pool (mc.conv_bn_act_maxpool)
             return mc.conv_bn_act_maxpool(x, self.conv1, self.bn1, ACT_RELU, 3, 2, 1)
+        ad = mc.bn_adapting(self.bn1) if not self.bn1.training else None
+        if (ad is not None and not ad.frozen and getattr(be, "name", "") == "hip" and x.is_cuda
+                and x.dtype == torch.float32 and os.environ.get("MX_STEM_FUSED", "1") != "0"):
+            # test-time BN adaptation (mx_det.adapt): the frozen-stem route with the adaptive finalize
+            return mc.conv_bn_act_maxpool(x, self.conv1, self.bn1, ACT_RELU, 3, 2, 1, adapt=ad)
         x = be.conv_bn(x, self.conv1, self.bn1, ACT_RELU)
         return be.maxpool(x, 3, 2, 1)
 

@@ -8,14 +8,20 @@ per_class_ap50}}}) and experiments/eval_results.csv. torchrun shards the images 
 MX_EXTRA_VARIANTS=jpeg adds the Test_JPEG set (column JPEG) after the reference's four, and night / haze /
 rain the Test_Night / Test_Haze / Test_Rain sets (columns Night, Haze, Rain); MX_SEVERITIES
 (levels 1..5, default 3) adds the Test_<Kind>_s<L> sets after those (columns Noise-s1 and so on).
+MX_BN_ADAPT=<mode>[:<prior>] (batch or stream; prior in images, default 16; unset: off) evaluates every
+checkpoint a second time under test-time BatchNorm adaptation (mx_det.adapt) and adds it as
+<name>_BNAdapt next to the unadapted entry, in the same schema; MX_BN_ADAPT_FREEZE_AFTER=<images>
+freezes the stream-mode statistics after that many images of each variant.
 """
 import csv
 import json
+import os
 import time
 from pathlib import Path
 
 import torch
 
+from mx_det import adapt as bn_adapt
 from mx_det.augment import EXTRA_VARIANTS, env_extra_variants, severity_variants
 from mx_det.engine import dist_info, eval_frcnn_variant, init_device, load_frcnn_checkpoint
 
@@ -49,20 +55,26 @@ def variant_paths(root, v):
     return str(root / v / "images" / "val"), str(root / v / "annotations" / "instances_val.json")
 
 
-def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None, restore_clean=False, counts=None):
+ADAPT_SUFFIX = "_BNAdapt"
+
+
+def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None, restore_clean=False, counts=None, adapt=None):
     """restore_clean: apply `restorer` to Test_Clean as well (a blind mx_det.gate.GatedRestorer decides per
     image, so the directory name no longer does). counts: a dict that receives the restorer's
-    take_counts() per variant (this rank's shard)."""
+    take_counts() per variant (this rank's shard). adapt: (mode, prior) of a mx_det.adapt.BNAdapter for the
+    model, reset at the start of every variant (None: the running statistics, as the reference)."""
     rank = dist_info()[1]
     root = COCO_TESTSET_ROOT if root is None else root
     variants = all_variants() if variants is None else variants
     if rank == 0:
         print("=" * 60 + f"\n  {name}  (COCOeval bbox)\n" + "=" * 60, flush=True)
     model = load_frcnn_checkpoint(ckpt, dev)
+    kw = {} if adapt is None else dict(adapter=bn_adapt.BNAdapter(model, mode=adapt[0], prior=adapt[1]))
     res = {}
     for v in variants:
         img_dir, ann = variant_paths(root, v)
-        m = eval_frcnn_variant(model, img_dir, ann, dev, restorer=restorer if restore_clean or v != "Test_Clean" else None)
+        m = eval_frcnn_variant(model, img_dir, ann, dev, restorer=restorer if restore_clean or v != "Test_Clean" else None,
+                               **kw)
         if counts is not None and restorer is not None:
             counts[v] = restorer.take_counts()
         if rank == 0:
@@ -82,7 +94,7 @@ def save_json(all_results, path):
 def save_csv(all_results, path, variants=None, pairs=None):
     variants = all_variants() if variants is None else variants
     pairs = BASELINE_PAIRS if pairs is None else pairs
-    models = [m for m in MODEL_ORDER if m in all_results]
+    models = [m for base in MODEL_ORDER for m in (base, base + ADAPT_SUFFIX) if m in all_results]
     with open(path, "w", newline="", encoding="utf-8") as f:
         w = csv.writer(f)
         w.writerow(["Model", "Metric"] + [short(v) for v in variants])
@@ -106,12 +118,17 @@ def save_csv(all_results, path, variants=None, pairs=None):
 
 def main():
     dev, world, rank = init_device()
+    adapt = bn_adapt.parse_env(os.environ.get("MX_BN_ADAPT", ""))  # a bad value raises before any model loads
     t0 = time.time()
     all_results = {}
     for name, ck in CKPTS.items():
         r = eval_model(name, ck, dev)
         if rank == 0:
             all_results[name] = r
+        if adapt is not None:
+            r = eval_model(name + ADAPT_SUFFIX, ck, dev, adapt=adapt)
+            if rank == 0:
+                all_results[name + ADAPT_SUFFIX] = r
     if rank == 0:
         print("\n  RT-DETR-L / YOLOv8m: Ultralytics branches not part of this build (skipped)")
         print(f"\nTotal evaluation time: {(time.time() - t0) / 60:.1f} min")

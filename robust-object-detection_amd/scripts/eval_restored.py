@@ -18,12 +18,15 @@ go to experiments/eval_restored_results_gated.json (reference schema), the per-v
 counts to experiments/restore_gate_counts.json.
 MX_EXTRA_VARIANTS=jpeg evaluates the restored Test_JPEG set too, MX_SEVERITIES the restored
 Test_<Kind>_s<L> sets (eval_all.all_variants()).
+MX_BN_ADAPT=<mode>[:<prior>] adds a <name>_BNAdapt entry per checkpoint: the same run with test-time BatchNorm
+adaptation of the detector (mx_det.adapt; the U-Net's BatchNorm stays folded), as in eval_all.
 """
 import os
 from pathlib import Path
 
 import torch
 
+from mx_det import adapt as bn_adapt
 from mx_det import gate
 from mx_det.unet import RestorationUNet
 from scripts import eval_all
@@ -53,6 +56,7 @@ def results_name(on_device, gated=False):
 def main():
     dev, world, rank = eval_all.init_device()
     on_device = os.environ.get("MX_RESTORE_ON_DEVICE", "0") != "0"
+    adapt = bn_adapt.parse_env(os.environ.get("MX_BN_ADAPT", ""))
     rules = gate.env_gate() if on_device else None  # a bad rules file raises here, before any model loads
     restorer = load_unet(dev) if on_device else None
     root = CORRUPTED_ROOT if on_device else RESTORED_ROOT
@@ -67,6 +71,13 @@ def main():
         r = eval_all.eval_model(name, ck, dev, root=root, restorer=restorer, **kw)
         if rank == 0:
             results[name] = r
+        if adapt is not None:
+            aname = name + eval_all.ADAPT_SUFFIX
+            if rules is not None:
+                kw["counts"] = counts.setdefault(aname, {})
+            r = eval_all.eval_model(aname, ck, dev, root=root, restorer=restorer, adapt=adapt, **kw)
+            if rank == 0:
+                results[aname] = r
     if rank == 0:
         OUT_DIR.mkdir(parents=True, exist_ok=True)
         eval_all.save_json(results, OUT_DIR / results_name(on_device, rules is not None))
