@@ -572,7 +572,8 @@ int mx_conv2d_wgrad_ex(const mx_conv_shape* s, const uint16_t* dy, const uint16_
 /* fwd/dgrad operand loader knob: 1 (default) buffer descriptors with wave-uniform tap offsets where
  * the shape allows (input channels % 32 == 0, R*S <= 64, operands < 2 GiB), 0 per-lane global loads. */
 int mx_conv_set_loader(int loader);
-/* fwd/dgrad block-tile override for tuning: (0, 0) automatic, else rows 64/128 x columns 64/128/256. */
+/* fwd/dgrad block-tile override for tuning: (0, 0) automatic, else rows 64/128/256 x columns 64/128/256
+ * (256 rows: the bf16x3 kernels only, as 256 x 128 tiles; the bf16 kernels run 128 rows instead). */
 int mx_conv_set_tile(int block_rows, int block_cols);
 /* Upper bound on the split-K factor of fwd / dgrad launches (0 = automatic; tuning only). */
 int mx_conv_set_max_splits(int max_splits);
@@ -589,7 +590,9 @@ int mx_conv_set_wgrad_target(int64_t blocks);
  * a buffer-descriptor kernel ran, out[6] kernel kind (bf16 fwd/dgrad: the mx_conv_set_variant number
  * launched; bf16 wgrad: the mx_conv_set_wgrad_variant number launched, 0 when the buffer kernel's map
  * guard fell back to the register kernel; bf16x3 fwd/dgrad: 100 + the mx_conv_set_stages alternative;
- * bf16x3 wgrad: 103 / 104 / 105 for the 128x128 / 128x256 / 256x256 block), out[7] launches the entry
+ * bf16x3 wgrad: 103 / 104 / 105 for the 128x128 / 128x256 / 256x256 block, 106 for the tile-list
+ * 128x128 wgrad (mx_conv2d_wgrad_x3_rows); 107 for the rows dgrad (mx_conv2d_dgrad_x3_rows), whose out[3]
+ * is 1 and out[4] the blocks launched for the list's capacity), out[7] launches the entry
  * has issued (stride-2 dgrad: the non-empty parity classes; the record is that of the last one).
  * MX_EINVAL before the thread's first launch. */
 int mx_conv_last_launch(int32_t out[8]);

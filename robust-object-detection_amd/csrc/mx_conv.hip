@@ -2754,12 +2754,13 @@ extern "C" int mx_conv_set_korder(int v) {
 }
 
 // The last conv launch of the calling thread (mx_conv_last_launch): written by launch_igemm,
-// launch_igemm_x3 and the two wgrad entries, so a test can assert the path a shape really took.
+// launch_igemm_x3, the wgrad entries and the rows dgrad, so a test can assert the path a shape really took.
 // [0] pass (0 fwd, 1 dgrad, 2 wgrad), [1] block rows, [2] block columns, [3] K / pixel splits launched,
 // [4] output tiles, [5] 1 = buffer-descriptor kernel, [6] kernel kind (bf16 fwd/dgrad: the variant
 // 0..9 launched; bf16 wgrad: 0 px32, 1 px64, 2 direct-to-LDS, 3 buffer; bf16x3: 100 + the ring /
 // wave-tile alternative (mx_conv_set_stages) for fwd/dgrad, 100 + 3 / 4 / 5 (128x128, 128x256,
-// 256x256 block) for wgrad, 106 the tile-list 128x128 wgrad), [7] launches issued by the entry so far (dgrad: non-empty parity classes)
+// 256x256 block) for wgrad, 106 the tile-list 128x128 wgrad, 107 the rows dgrad), [7] launches issued by
+// the entry so far (dgrad: non-empty parity classes)
 static thread_local int32_t g_last_launch[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
 static thread_local int32_t g_launch_count = 0;  // reset by each entry point, counted per launch
 static void record_launch(int pass, int bmt, int bn, int64_t splits, int64_t tiles, bool buf, int kind) {
@@ -2781,7 +2782,28 @@ struct Geo {
   int splits, bmt, bn;
   bool narrow;
 };
-static int num_cus();
+static int g_num_cus = 0;
+static int num_cus() {
+  if (!g_num_cus) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+      g_num_cus = n;
+    else
+      g_num_cus = 256;
+  }
+  return g_num_cus;
+}
+
+// the split-K factor of a geometry with tiles and nk set, under the cfg's cap
+static int geo_splits(const Cfg& cf, const Geo& g) {
+  int splits = 1;
+  if (g.Ncol % 8 == 0 && g.tiles < 320 && g.nk >= 8) {
+    int64_t sp = std::min<int64_t>(std::min<int64_t>(cdiv(640, g.tiles), g.nk / 4), 16);
+    splits = (int)std::max<int64_t>(1, sp);
+  }
+  if (cf.k.max_splits && splits > cf.k.max_splits) splits = cf.k.max_splits;
+  return splits;
+}
 
 static Geo make_geo(const Cfg& cf, int64_t M, int64_t Ncol, int64_t Kdim) {
   Geo g;
@@ -2826,13 +2848,7 @@ static Geo make_geo(const Cfg& cf, int64_t M, int64_t Ncol, int64_t Kdim) {
     g.tiles = cdiv(g.M, g.bmt) * cdiv(g.Ncol, g.bn);
   }
   g.nk = cdiv(g.Kdim, BK);
-  g.splits = 1;
-  const int64_t split_below = 320;
-  if (cf.variant >= 1 && g.Ncol % 8 == 0 && g.tiles < split_below && g.nk >= 8) {
-    int64_t sp = std::min<int64_t>(std::min<int64_t>(cdiv(640, g.tiles), g.nk / 4), 16);
-    g.splits = (int)std::max<int64_t>(1, sp);
-  }
-  if (cf.k.max_splits && g.splits > cf.k.max_splits) g.splits = cf.k.max_splits;
+  g.splits = cf.variant >= 1 ? geo_splits(cf, g) : 1;  // variant 0 (register staging) is never split
   return g;
 }
 
@@ -2850,28 +2866,24 @@ static int launch_kind(const Cfg& cf, const Geo& g) {
   return c4 < c3 ? 4 : 3;
 }
 
-static size_t wgrad_ws(const Cfg& cf, const mx_conv_shape* s);
+// Bytes of a split workspace, one f32 [rows][cols] partial per split (0: not split). The launchers
+// check against it and the workspace queries (conv_workspace) answer with it.
+static size_t split_ws_bytes(int64_t splits, int64_t rows, int64_t cols) {
+  return splits > 1 ? sizeof(float) * (size_t)splits * rows * cols : 0;
+}
 
-extern "C" size_t mx_conv_workspace(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg) {
-  Cfg cf;
-  if (!s || pass < 0 || pass > 2 || resolve_cfg(cfg, cf)) return 0;
-  if (pass == 2) return wgrad_ws(cf, s);
-  if (pass == 0) {
-    Geo g = make_geo(cf, s->N * s->Ho * s->Wo, s->K, s->R * s->S * s->C);
-    return g.splits > 1 ? sizeof(float) * (size_t)g.splits * g.M * g.Ncol : 0;
-  }
-  if (s->stride_h < 1 || s->stride_h > 2 || s->stride_w < 1 || s->stride_w > 2) return 0;
+// The stride-parity classes of a dgrad that launch, in launch order: an empty class (H or W of 1 under
+// stride 2) has no rows to write. The dgrad entries and the workspace queries all walk this list, so
+// the workspace is the maximum over exactly the classes that run.
+static int dgrad_launch_classes(const mx_conv_shape* s, DClass out[4]) {
   DClass cl[4];
   int64_t off[4];
   int br[4], bs[4];
   const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
-  size_t mx = 0;
-  for (int i = 0; i < n; ++i) {
-    if (cl[i].Hc * cl[i].Wc == 0) continue;  // an empty parity class (H or W of 1) is not launched
-    Geo g = make_geo(cf, s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
-    if (g.splits > 1) mx = std::max(mx, sizeof(float) * (size_t)g.splits * g.M * g.Ncol);
-  }
-  return mx;
+  int m = 0;
+  for (int i = 0; i < n; ++i)
+    if (cl[i].Hc * cl[i].Wc != 0) out[m++] = cl[i];
+  return m;
 }
 
 template <int BN, int MODE, int BKT, int STAGES, int OCC, int BMT = BM>
@@ -2909,6 +2921,42 @@ static void launch_variant(int v, const ConvP& p, int64_t blocks, hipStream_t st
   }
 }
 
+// Split-K plan of one launch: the nk K-tiles (in the kernel's tile width) go in equal shares of whole
+// tiles to at most g.splits blocks per output tile, partials to the workspace (`query` names the function
+// that sizes it). Returns the splits launched, the factor on the grid; 0 with the error set when the
+// workspace is short.
+static int plan_splitk(ConvP& p, const Geo& g, int64_t nk, void* ws, size_t ws_bytes, const char* query) {
+  p.splits = 1;
+  p.kt_per_split = nk;
+  p.slab = nullptr;
+  if (g.splits <= 1) return 1;
+  const size_t need = split_ws_bytes(g.splits, g.M, g.Ncol);
+  if (!ws || ws_bytes < need) {
+    set_error("conv: split-K workspace of %zu bytes required (%s)", need, query);
+    return 0;
+  }
+  p.kt_per_split = cdiv(nk, (int64_t)g.splits);
+  p.splits = (int)cdiv(nk, p.kt_per_split);
+  p.slab = (float*)ws;
+  return p.splits;
+}
+
+// The reduce of a split launch (TA: the activation storage type, uint16_t bf16 or float). It works in
+// 128-row blocks; 16-column blocks when 64-column ones would not fill the chip.
+template <typename TA>
+static int launch_splitk_reduce(const ConvP& p, const Geo& g, hipStream_t st) {
+  if (!p.slab) return MX_OK;
+  if (cdiv(g.M, BM) * cdiv(g.Ncol, 64) >= 2 * (int64_t)num_cus()) {
+    dim3 rg((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.Ncol, 64));
+    conv_splitk_reduce_kernel<8, TA><<<rg, 256, 0, st>>>(p);
+  } else {
+    dim3 rg((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.Ncol, 16));
+    conv_splitk_reduce_kernel<2, TA><<<rg, 256, 0, st>>>(p);
+  }
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
 template <int MODE>
 static int launch_igemm(const Cfg& cf, ConvP& p, const Geo& g, void* ws, size_t ws_bytes, hipStream_t st) {
   int64_t blocks = g.tiles;
@@ -2919,18 +2967,9 @@ static int launch_igemm(const Cfg& cf, ConvP& p, const Geo& g, void* ws, size_t 
   MX_CHECK_ARG(buf || g.bn != 256 || g.bmt == BM, "conv: 64x256 tiles need the buffer loader");
   const int v = buf ? 3 : launch_kind(cf, g);
   const int64_t bkt = (buf || v == 3 || v == 5 || v == 8 || v == 9) ? 32 : 64;
-  const int64_t nk = cdiv(g.Kdim, bkt);  // K-tiles in the kernel's tile width
-  p.splits = 1;
-  p.kt_per_split = nk;
-  p.slab = nullptr;
-  if (g.splits > 1) {
-    size_t need = sizeof(float) * (size_t)g.splits * g.M * g.Ncol;
-    MX_CHECK_ARG(ws && ws_bytes >= need, "conv: split-K workspace of %zu bytes required (mx_conv_workspace)", need);
-    p.kt_per_split = cdiv(nk, (int64_t)g.splits);
-    p.splits = (int)cdiv(nk, p.kt_per_split);
-    p.slab = (float*)ws;
-    blocks *= p.splits;
-  }
+  const int splits = plan_splitk(p, g, cdiv(g.Kdim, bkt), ws, ws_bytes, "mx_conv_workspace");
+  if (!splits) return MX_EINVAL;
+  blocks *= splits;
   if (buf) {
     p.korder = cf.korder;
     if (cf.loader == 2) p.src_elems = 0;
@@ -2951,18 +2990,18 @@ static int launch_igemm(const Cfg& cf, ConvP& p, const Geo& g, void* ws, size_t 
   else launch_variant<128, MODE>(v, p, blocks, st);
   MX_LAUNCH_CHECK();
   record_launch(MODE, g.bmt, g.bn, p.splits, g.tiles, buf, buf ? 3 : (g.bn == 256 ? 9 : v));
-  if (p.slab) {
-    // the reduce works in 128-row blocks; 16-column blocks when 64-column ones would not fill the chip
-    if (cdiv(g.M, BM) * cdiv(g.Ncol, 64) >= 2 * (int64_t)num_cus()) {
-      dim3 rg((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.Ncol, 64));
-      conv_splitk_reduce_kernel<8><<<rg, 256, 0, st>>>(p);
-    } else {
-      dim3 rg((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.Ncol, 16));
-      conv_splitk_reduce_kernel<2><<<rg, 256, 0, st>>>(p);
-    }
-    MX_LAUNCH_CHECK();
-  }
-  return MX_OK;
+  return launch_splitk_reduce<uint16_t>(p, g, st);
+}
+
+// The forward GEMM of a conv: rows = output pixels, columns = output channels, K = (r, s, c). The entry
+// adds its epilogue (bias, residual, act, out, stats) and, for the bf16x3 kernels, the weight's lo plane.
+static void fill_fwd(ConvP& p, const mx_conv_shape* s, const void* src, const uint16_t* wt) {
+  p.src = (const uint16_t*)src; p.wt = wt;
+  p.M = s->N * s->Ho * s->Wo; p.Ncol = s->K; p.Kdim = s->R * s->S * s->C;
+  p.OH = s->Ho; p.OW = s->Wo; p.IH = s->H; p.IW = s->W; p.IC = s->C;
+  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
+  p.mblocks = cdiv(p.M, SROWS);
+  p.src_elems = s->N * s->H * s->W * s->C; p.wt_elems = p.Ncol * p.Kdim;
 }
 
 extern "C" int mx_conv2d_fwd_ex(const mx_conv_shape* s, const uint16_t* x, const uint16_t* w, const float* bias,
@@ -2977,13 +3016,8 @@ extern "C" int mx_conv2d_fwd_ex(const mx_conv_shape* s, const uint16_t* x, const
   MX_CHECK_ARG(ydtype == MX_BF16 || ydtype == MX_F32, "conv fwd: bad output dtype");
   MX_CHECK_ARG(!residual || s->K % 8 == 0, "conv fwd: residual needs K %% 8 == 0");
   ConvP p{};
-  p.src = x; p.wt = w;
-  p.M = s->N * s->Ho * s->Wo; p.Ncol = s->K; p.Kdim = s->R * s->S * s->C;
-  p.OH = s->Ho; p.OW = s->Wo; p.IH = s->H; p.IW = s->W; p.IC = s->C;
-  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
-  p.bias = bias; p.residual = residual; p.act = act; p.out = y; p.out_f32 = ydtype == MX_F32;
-  p.stats = stats; p.mblocks = cdiv(p.M, SROWS);
-  p.src_elems = s->N * s->H * s->W * s->C; p.wt_elems = p.Ncol * p.Kdim;
+  fill_fwd(p, s, x, w);
+  p.bias = bias; p.residual = residual; p.act = act; p.out = y; p.out_f32 = ydtype == MX_F32; p.stats = stats;
   g_launch_count = 0;
   return launch_igemm<0>(cf, p, make_geo(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
 }
@@ -3019,16 +3053,53 @@ extern "C" int mx_conv2d_dgrad_t(const mx_conv_shape* s, const uint16_t* dy, con
 }
 
 struct BnbArgs {
-  const uint16_t *y, *z;
+  const void *y, *z;  // activation storage, bf16 or f32 as dx
   const float *mean, *invstd;
   int act;
   float* part;
   int64_t mb;
 };
 
+// The GEMM of one dgrad parity class: rows = the class's dx pixels, columns = input channels, K = the
+// class's taps x output channels, a stride-1 gather of dy; rows land in the full dx grid through the
+// remap fields. residual: a gradient accumulated in the epilogue; under stride 2 each parity class adds
+// it at the pixels it writes (classes without taps write it alone), so every pixel gets it exactly once.
+// The bf16x3 entries add out_f32 and the weight's lo plane.
+static void fill_dgrad_class(ConvP& p, const mx_conv_shape* s, const DClass& c, const void* dy, const uint16_t* wt,
+                             const void* residual, void* dx, const BnbArgs* bnb) {
+  p.src = (const uint16_t*)dy; p.wt = wt + c.off;
+  p.M = s->N * c.Hc * c.Wc; p.Ncol = s->C; p.Kdim = (int64_t)c.Rc * c.Sc * s->K;
+  p.OH = c.Hc; p.OW = c.Wc; p.IH = s->Ho; p.IW = s->Wo; p.IC = s->K;
+  p.R = std::max(c.Rc, 1); p.S = std::max(c.Sc, 1); p.st_h = 1; p.st_w = 1; p.pad_h = c.dh; p.pad_w = c.dw;
+  p.out = dx; p.out_f32 = 0; p.act = 0; p.residual = residual;
+  if (bnb) {
+    p.bnb_y = bnb->y; p.bnb_z = bnb->z; p.bnb_mean = bnb->mean; p.bnb_invstd = bnb->invstd;
+    p.bnb_act = bnb->act; p.bnb_part = bnb->part; p.bnb_mb = bnb->mb;
+  }
+  p.remap = s->stride_h > 1 || s->stride_w > 1; p.rst_h = s->stride_h; p.rst_w = s->stride_w; p.rph = c.ph; p.rpw = c.pw;
+  p.rH = s->H; p.rW = s->W;
+  p.src_elems = s->N * s->Ho * s->Wo * s->K; p.wt_elems = p.Ncol * p.Kdim;
+}
+
 static int dgrad_impl(const Cfg& cf, const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt,
                       const uint16_t* residual, uint16_t* dx, const BnbArgs* bnb, void* ws, size_t ws_bytes,
-                      mx_stream_t stream);
+                      mx_stream_t stream) {
+  int rc = conv_check(s);
+  if (rc) return rc;
+  MX_CHECK_ARG(s->K % 8 == 0, "conv dgrad: K=%lld must be a multiple of 8", (long long)s->K);
+  MX_CHECK_ARG(s->C % 8 == 0, "conv dgrad: C=%lld must be a multiple of 8", (long long)s->C);
+  MX_CHECK_ARG(s->stride_h <= 2 && s->stride_w <= 2, "conv dgrad: strides 1 and 2 are supported");
+  DClass cl[4];
+  const int n = dgrad_launch_classes(s, cl);
+  g_launch_count = 0;
+  for (int i = 0; i < n; ++i) {
+    ConvP p{};
+    fill_dgrad_class(p, s, cl[i], dy, wt, residual, dx, bnb);
+    rc = launch_igemm<1>(cf, p, make_geo(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
+    if (rc) return rc;
+  }
+  return MX_OK;
+}
 
 extern "C" int mx_conv2d_dgrad_ex(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt,
                                   const uint16_t* residual, uint16_t* dx, void* ws, size_t ws_bytes,
@@ -3050,44 +3121,6 @@ extern "C" int mx_conv2d_dgrad_bnb(const mx_conv_shape* s, const uint16_t* dy, c
   MX_CHECK_ARG(part_mb == cdiv(s->N * s->H * s->W, 64), "conv dgrad bnb: part rows must be cdiv(N*H*W, 64)");
   BnbArgs b{y, z, mean, invstd, act, part, part_mb};
   return dgrad_impl(cf, s, dy, wt, residual, dx, &b, ws, ws_bytes, stream);
-}
-
-static int dgrad_impl(const Cfg& cf, const mx_conv_shape* s, const uint16_t* dy, const uint16_t* wt,
-                      const uint16_t* residual, uint16_t* dx, const BnbArgs* bnb, void* ws, size_t ws_bytes,
-                      mx_stream_t stream) {
-  // residual: a gradient accumulated in the epilogue; under stride 2 each parity class adds it at the
-  // pixels it writes (classes without taps write it alone), so every pixel gets it exactly once
-  int rc = conv_check(s);
-  if (rc) return rc;
-  MX_CHECK_ARG(s->K % 8 == 0, "conv dgrad: K=%lld must be a multiple of 8", (long long)s->K);
-  MX_CHECK_ARG(s->C % 8 == 0, "conv dgrad: C=%lld must be a multiple of 8", (long long)s->C);
-  MX_CHECK_ARG(s->stride_h <= 2 && s->stride_w <= 2, "conv dgrad: strides 1 and 2 are supported");
-  DClass cl[4];
-  int64_t off[4];
-  int br[4], bs[4];
-  const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
-  const bool remap = s->stride_h > 1 || s->stride_w > 1;
-  g_launch_count = 0;
-  for (int i = 0; i < n; ++i) {
-    const DClass& c = cl[i];
-    if (c.Hc * c.Wc == 0) continue;
-    ConvP p{};
-    p.src = dy; p.wt = wt + c.off;
-    p.M = s->N * c.Hc * c.Wc; p.Ncol = s->C; p.Kdim = (int64_t)c.Rc * c.Sc * s->K;
-    p.OH = c.Hc; p.OW = c.Wc; p.IH = s->Ho; p.IW = s->Wo; p.IC = s->K;
-    p.R = std::max(c.Rc, 1); p.S = std::max(c.Sc, 1); p.st_h = 1; p.st_w = 1; p.pad_h = c.dh; p.pad_w = c.dw;
-    p.out = dx; p.out_f32 = 0; p.act = 0; p.residual = residual;
-    if (bnb) {
-      p.bnb_y = bnb->y; p.bnb_z = bnb->z; p.bnb_mean = bnb->mean; p.bnb_invstd = bnb->invstd;
-      p.bnb_act = bnb->act; p.bnb_part = bnb->part; p.bnb_mb = bnb->mb;
-    }
-    p.remap = remap; p.rst_h = s->stride_h; p.rst_w = s->stride_w; p.rph = c.ph; p.rpw = c.pw;
-    p.rH = s->H; p.rW = s->W;
-    p.src_elems = s->N * s->Ho * s->Wo * s->K; p.wt_elems = p.Ncol * p.Kdim;
-    rc = launch_igemm<1>(cf, p, make_geo(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
-    if (rc) return rc;
-  }
-  return MX_OK;
 }
 
 extern "C" int mx_conv2d_dgrad(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* w, uint16_t* dx,
@@ -3128,31 +3161,39 @@ struct WGeo {
   int64_t tiles, splits, kchunk;
   int pxt;
 };
-static int g_num_cus = 0;
-static int num_cus() {
-  if (!g_num_cus) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      g_num_cus = n;
-    else
-      g_num_cus = 256;
-  }
-  return g_num_cus;
-}
-static WGeo wgrad_geo(const Cfg& cf, const mx_conv_shape* s) {
-  WGeo g;
-  const int64_t P = s->N * s->Ho * s->Wo, Ncol = s->R * s->S * s->C;
-  g.tiles = cdiv(s->K, 128) * cdiv(Ncol, 128);
-  const int v = cf.k.wgrad_variant >= 4 ? 3 : cf.k.wgrad_variant;
-  g.pxt = v == 2 ? BKG : (v == 1 ? 64 : BKW);
-  // resident blocks per CU: px32 / buffer 3 (142 VGPRs), px64 / direct-to-LDS 2
-  const int64_t slots = cf.k.wgrad_target ? cf.k.wgrad_target : (int64_t)num_cus() * ((v == 0 || v == 3) ? 3 : 2);
-  int64_t splits = std::max<int64_t>(1, slots / g.tiles);  // never past one wave of blocks
+// the pixel split of g.tiles tiles of g.pxt-pixel K-tiles: towards wgrad_target blocks, or one wave at
+// `occ` resident blocks per CU; never past that, and at least 4 K-tiles per split
+static WGeo wgrad_split(const Cfg& cf, const mx_conv_shape* s, WGeo g, int occ) {
+  const int64_t P = s->N * s->Ho * s->Wo;
+  const int64_t slots = cf.k.wgrad_target ? cf.k.wgrad_target : (int64_t)num_cus() * occ;
+  int64_t splits = std::max<int64_t>(1, slots / g.tiles);
   const int64_t max_splits = std::max<int64_t>(1, P / (g.pxt * 4));
   splits = std::min(splits, max_splits);
   g.kchunk = cdiv(cdiv(P, splits), g.pxt) * g.pxt;
   g.splits = cdiv(P, g.kchunk);
   return g;
+}
+static WGeo wgrad_geo(const Cfg& cf, const mx_conv_shape* s) {
+  WGeo g{};
+  g.tiles = cdiv(s->K, 128) * cdiv(s->R * s->S * s->C, 128);
+  const int v = cf.k.wgrad_variant >= 4 ? 3 : cf.k.wgrad_variant;
+  g.pxt = v == 2 ? BKG : (v == 1 ? 64 : BKW);
+  // resident blocks per CU: px32 / buffer 3 (142 VGPRs), px64 / direct-to-LDS 2
+  return wgrad_split(cf, s, g, (v == 0 || v == 3) ? 3 : 2);
+}
+
+// bf16x3 wgrad block shape: 128 x 128 (4 waves, 2 blocks per CU) unless wide, 128 x 256 (8 waves, one
+// block per CU; mx_conv_set_wgrad_variant(4) -- a tuner candidate)
+static bool wgrad_x3_wide(const Cfg& cf) { return cf.k.wgrad_variant == 4; }
+// 5: 256 x 256 tile, one wave per SIMD (conv_wgrad_x3ww_kernel; a tuner candidate)
+static bool wgrad_x3_ww(const Cfg& cf) { return cf.k.wgrad_variant == 5; }
+static WGeo wgrad_geo_x3(const Cfg& cf, const mx_conv_shape* s) {
+  WGeo g{};
+  const int64_t Ncol = s->R * s->S * s->C;
+  const bool wide = wgrad_x3_wide(cf), ww = wgrad_x3_ww(cf);
+  g.tiles = ww ? cdiv(s->K, 256) * cdiv(Ncol, 256) : cdiv(s->K, 128) * cdiv(Ncol, wide ? 256 : 128);
+  g.pxt = 32;
+  return wgrad_split(cf, s, g, (wide || ww) ? 1 : 2);
 }
 
 // A dense conv (valid RxS on an RxS map: one output pixel per image, FC6 as a 7x7 conv) has the
@@ -3170,52 +3211,80 @@ static mx_conv_shape wgrad_shape(const mx_conv_shape* s, bool* dense) {
   return d;
 }
 
-static size_t wgrad_ws(const Cfg& cf, const mx_conv_shape* s0) {
+// The wgrad entries (bf16, bf16x3, bf16x3 tile-list) share their prologue and epilogue: wgrad_check,
+// fill_wgrad, for the x3 kernels wgrad_x3_ranges, then the entry's own kernel and launch record, then
+// wgrad_finish. `name` is the entry's error-message prefix.
+static int wgrad_check(const mx_conv_shape* s, int64_t Kout, int64_t Cin, int layout, const char* name) {
+  int rc = conv_check(s);
+  if (rc) return rc;
+  MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "%s: K and C must be multiples of 8", name);
+  MX_CHECK_ARG(Kout >= 1 && Kout <= s->K && Cin >= 1 && Cin <= s->C, "%s: Kout/Cin out of range", name);
+  MX_CHECK_ARG(layout == 0 || layout == 1, "%s: layout 0 (KRSC) or 1 (KCRS)", name);
+  MX_CHECK_ARG(s->K * s->R * s->S * s->C < (1ll << 31), "%s: weight too large", name);
+  return MX_OK;
+}
+
+// Fills p for the conv s0 in the form it launches in (wgrad_shape) and returns that form's geometry in
+// g; a split geometry takes the workspace (`query` names the function that sizes it) as its slab.
+static int fill_wgrad(WgP& p, WGeo& g, const Cfg& cf, WGeo (*geo)(const Cfg&, const mx_conv_shape*),
+                      const mx_conv_shape* s0, const void* dy, const void* x, float* dw, int64_t Kout, int64_t Cin,
+                      int layout, void* ws, size_t ws_bytes, const char* name, const char* query) {
   bool dense;
   const mx_conv_shape sd = wgrad_shape(s0, &dense);
   const mx_conv_shape* s = &sd;
-  WGeo g = wgrad_geo(cf, s);
-  return g.splits > 1 ? sizeof(float) * (size_t)g.splits * s->K * s->R * s->S * s->C : 0;
+  p.dy = (const uint16_t*)dy; p.x = (const uint16_t*)x; p.dw = dw;
+  p.P = s->N * s->Ho * s->Wo; p.K = s->K; p.Ncol = s->R * s->S * s->C;
+  p.OH = s->Ho; p.OW = s->Wo; p.H = s->H; p.W = s->W; p.C = s->C; p.N = s->N;
+  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
+  p.Kout = Kout; p.Cin = Cin; p.layout = layout;
+  p.dC = (int)s0->C; p.dRS = (int)(s0->R * s0->S);
+  g = geo(cf, s);
+  p.kchunk = g.kchunk;
+  if (g.splits > 1) {
+    const size_t need = split_ws_bytes(g.splits, p.K, p.Ncol);
+    MX_CHECK_ARG(ws && ws_bytes >= need, "%s: split workspace of %zu bytes required (%s pass 2)", name, need, query);
+    p.slab = (float*)ws;
+  }
+  return MX_OK;
+}
+
+// the grid and the 32-bit / 24-bit offset math of the bf16x3 wgrad kernels
+static int wgrad_x3_ranges(const WgP& p, const WGeo& g, const char* name) {
+  MX_CHECK_ARG(g.tiles * g.splits < (1ll << 31), "%s: grid too large", name);
+  MX_CHECK_ARG(p.P * p.K * 4 < (1ll << 31) && p.N * p.H * p.W * p.C * 4 < (1ll << 31) && p.P + 64 < (1ll << 23) &&
+                   p.N * p.H * p.W < (1ll << 23) && p.K * 4 < (1ll << 24) && p.C * 4 < (1ll << 24),
+               "%s: dy / x must each stay below 2 GiB and 8M pixels (32-bit / 24-bit offset math)", name);
+  return MX_OK;
+}
+
+// after the entry's kernel: the sum of a split launch's partials into dw
+static int wgrad_finish(const WgP& p, const WGeo& g, int64_t Kout, hipStream_t st, const char* name) {
+  if (g.splits <= 1) return MX_OK;
+  MX_CHECK_ARG(Kout < 65536, "%s: too many output channels for the split reduce", name);
+  wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
 }
 
 extern "C" int mx_conv2d_wgrad_ex(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* x, float* dw,
                                   int64_t Kout, int64_t Cin, int layout, void* ws, size_t ws_bytes,
                                   mx_stream_t stream, const mx_conv_cfg* cfg) {
+  const char* name = "conv wgrad";
   Cfg cf;
   int rc = resolve_cfg(cfg, cf);
+  if (!rc) rc = wgrad_check(s, Kout, Cin, layout, name);
   if (rc) return rc;
-  rc = conv_check(s);
-  if (rc) return rc;
-  MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "conv wgrad: K and C must be multiples of 8");
-  MX_CHECK_ARG(Kout >= 1 && Kout <= s->K && Cin >= 1 && Cin <= s->C, "conv wgrad: Kout/Cin out of range");
-  MX_CHECK_ARG(layout == 0 || layout == 1, "conv wgrad: layout 0 (KRSC) or 1 (KCRS)");
-  MX_CHECK_ARG(s->K * s->R * s->S * s->C < (1ll << 31), "conv wgrad: weight too large");
   hipStream_t st = (hipStream_t)stream;
-  const int dC = (int)s->C, dRS = (int)(s->R * s->S);
-  bool dense;
-  const mx_conv_shape sd = wgrad_shape(s, &dense);
-  s = &sd;
   WgP p{};
-  p.dy = dy; p.x = x; p.dw = dw;
-  p.P = s->N * s->Ho * s->Wo; p.K = s->K; p.Ncol = s->R * s->S * s->C;
-  p.OH = s->Ho; p.OW = s->Wo; p.H = s->H; p.W = s->W; p.C = s->C; p.N = s->N;
-  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
-  p.Kout = Kout; p.Cin = Cin; p.layout = layout;
-  p.dC = dC; p.dRS = dRS;
-  WGeo g = wgrad_geo(cf, s);
-  p.kchunk = g.kchunk;
-  if (g.splits > 1) {
-    const size_t need = sizeof(float) * (size_t)g.splits * p.K * p.Ncol;
-    MX_CHECK_ARG(ws && ws_bytes >= need, "conv wgrad: split workspace of %zu bytes required (mx_conv_workspace pass 2)",
-                 need);
-    p.slab = (float*)ws;
-  }
+  WGeo g;
+  rc = fill_wgrad(p, g, cf, wgrad_geo, s, dy, x, dw, Kout, Cin, layout, ws, ws_bytes, name, "mx_conv_workspace");
+  if (rc) return rc;
   MX_CHECK_ARG(g.tiles < (1ll << 31) && g.splits < 65536, "conv wgrad: grid too large");
   dim3 grid((unsigned)g.tiles, (unsigned)g.splits);
   int v = cf.k.wgrad_variant >= 4 ? 3 : cf.k.wgrad_variant;
   // the buffer kernel walks each lane's pixels by (n, oh, ow) increments: maps of fewer than 32
   // output pixels (FC6 as a 7x7 conv on the RoI tile) would wrap many times per tile -> register kernel
-  if (v == 3 && !(p.P * p.K * 2 < (1ll << 31) && s->N * s->H * s->W * s->C * 2 < (1ll << 31) &&
+  if (v == 3 && !(p.P * p.K * 2 < (1ll << 31) && p.N * p.H * p.W * p.C * 2 < (1ll << 31) &&
                  (p.OH * p.OW >= 32 || (p.OH == 1 && p.OW == 1))))
     v = 0;
   if (v == 3) conv_wgrad_buf_kernel<<<(unsigned)(g.tiles * g.splits), NT, 3 * 2 * 32 * 256, st>>>(p);
@@ -3225,12 +3294,7 @@ extern "C" int mx_conv2d_wgrad_ex(const mx_conv_shape* s, const uint16_t* dy, co
   MX_LAUNCH_CHECK();
   g_launch_count = 0;
   record_launch(2, 128, 128, g.splits, g.tiles, v == 3, v);
-  if (g.splits > 1) {
-    MX_CHECK_ARG(Kout < 65536, "conv wgrad: too many output channels for the split reduce");
-    wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);
-    MX_LAUNCH_CHECK();
-  }
-  return MX_OK;
+  return wgrad_finish(p, g, Kout, st, name);
 }
 
 extern "C" int mx_conv2d_wgrad(const mx_conv_shape* s, const uint16_t* dy, const uint16_t* x, float* dw, mx_stream_t stream) {
@@ -3272,12 +3336,7 @@ static Geo make_geo_x3(const Cfg& cf, int64_t M, int64_t Ncol, int64_t Kdim) {
     g.tiles = cdiv(M, g.bmt) * cdiv(Ncol, g.bn);
   }
   g.nk = cdiv(Kdim, 32);
-  g.splits = 1;
-  if (Ncol % 8 == 0 && g.tiles < 320 && g.nk >= 8) {
-    int64_t sp = std::min<int64_t>(std::min<int64_t>(cdiv(640, g.tiles), g.nk / 4), 16);
-    g.splits = (int)std::max<int64_t>(1, sp);
-  }
-  if (cf.k.max_splits && g.splits > cf.k.max_splits) g.splits = cf.k.max_splits;
+  g.splits = geo_splits(cf, g);
   // the splits the launch fills (equal shares of whole K-tiles): the workspace holds no unused slab
   if (g.splits > 1) g.splits = (int)cdiv(g.nk, cdiv(g.nk, (int64_t)g.splits));
   return g;
@@ -3310,18 +3369,9 @@ static int launch_igemm_x3(const Cfg& cf, ConvP& p, const Geo& g0, void* ws, siz
   MX_CHECK_ARG(g.Kdim < (1ll << 30) && p.IH < (1ll << 26) && p.IW < (1ll << 26) && p.IC < (1ll << 30),
                "conv: GEMM K or spatial size too large");
   MX_CHECK_ARG(p.IC % 8 == 0 && p.Kdim % 8 == 0, "conv x3: channel counts must be multiples of 8");
-  const int64_t nk = cdiv(g.Kdim, 32);
-  p.splits = 1;
-  p.kt_per_split = nk;
-  p.slab = nullptr;
-  if (g.splits > 1) {
-    const size_t need = sizeof(float) * (size_t)g.splits * g.M * g.Ncol;
-    MX_CHECK_ARG(ws && ws_bytes >= need, "conv: split-K workspace of %zu bytes required (mx_conv_workspace_x3)", need);
-    p.kt_per_split = cdiv(nk, (int64_t)g.splits);
-    p.splits = (int)cdiv(nk, p.kt_per_split);
-    p.slab = (float*)ws;
-    blocks *= p.splits;
-  }
+  const int splits = plan_splitk(p, g, cdiv(g.Kdim, 32), ws, ws_bytes, "mx_conv_workspace_x3");
+  if (!splits) return MX_EINVAL;
+  blocks *= splits;
   MX_CHECK_ARG(blocks < (1ll << 31), "conv: grid too large");
   if (buf) {
     // ring depth x blocks per CU; mx_conv_set_stages(3) picks the alternative of each tile shape
@@ -3357,64 +3407,40 @@ static int launch_igemm_x3(const Cfg& cf, ConvP& p, const Geo& g0, void* ws, siz
   }
   MX_LAUNCH_CHECK();
   record_launch(MODE, g.bmt, g.bn, p.splits, g.tiles, buf, 100 + (buf ? cf.k.stages : 0));
-  if (p.slab) {
-    if (cdiv(g.M, BM) * cdiv(g.Ncol, 64) >= 2 * (int64_t)num_cus()) {
-      dim3 rg((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.Ncol, 64));
-      conv_splitk_reduce_kernel<8, float><<<rg, 256, 0, st>>>(p);
-    } else {
-      dim3 rg((unsigned)cdiv(g.M, BM), (unsigned)cdiv(g.Ncol, 16));
-      conv_splitk_reduce_kernel<2, float><<<rg, 256, 0, st>>>(p);
-    }
-    MX_LAUNCH_CHECK();
-  }
-  return MX_OK;
+  return launch_splitk_reduce<float>(p, g, st);
 }
 
-// wgrad x3 block shape: 0 = 128 x 128 (4 waves, 2 blocks per CU), 1 = 128 x 256 (8 waves, one block
-// per CU; mx_conv_set_wgrad_variant(4) -- a tuner candidate)
-static int wgrad_x3_wide(const Cfg& cf) { return cf.k.wgrad_variant == 4; }
-// 5: 256 x 256 tile, one wave per SIMD (conv_wgrad_x3ww_kernel; a tuner candidate)
-static int wgrad_x3_ww(const Cfg& cf) { return cf.k.wgrad_variant == 5; }
-static WGeo wgrad_geo_x3(const Cfg& cf, const mx_conv_shape* s) {
-  WGeo g;
-  const int64_t P = s->N * s->Ho * s->Wo, Ncol = s->R * s->S * s->C;
-  const bool wide = wgrad_x3_wide(cf), ww = wgrad_x3_ww(cf);
-  g.tiles = ww ? cdiv(s->K, 256) * cdiv(Ncol, 256) : cdiv(s->K, 128) * cdiv(Ncol, wide ? 256 : 128);
-  g.pxt = 32;
-  const int64_t slots = cf.k.wgrad_target ? cf.k.wgrad_target : (int64_t)num_cus() * ((wide || ww) ? 1 : 2);
-  int64_t splits = std::max<int64_t>(1, slots / g.tiles);
-  const int64_t max_splits = std::max<int64_t>(1, P / (g.pxt * 4));
-  splits = std::min(splits, max_splits);
-  g.kchunk = cdiv(cdiv(P, splits), g.pxt) * g.pxt;
-  g.splits = cdiv(P, g.kchunk);
-  return g;
-}
-
-extern "C" size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg) {
+// The one body of both workspace queries, over the geometry functions of the bf16 or the bf16x3 kernels:
+// pass 0 fwd, 1 dgrad (the largest of the classes that launch), 2 wgrad (in its dense form, as launched).
+static size_t conv_workspace(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg,
+                             Geo (*geo)(const Cfg&, int64_t, int64_t, int64_t),
+                             WGeo (*wgeo)(const Cfg&, const mx_conv_shape*)) {
   Cfg cf;
   if (!s || pass < 0 || pass > 2 || resolve_cfg(cfg, cf)) return 0;
   if (pass == 2) {
     bool dense;
     const mx_conv_shape sd = wgrad_shape(s, &dense);
-    const WGeo g = wgrad_geo_x3(cf, &sd);
-    return g.splits > 1 ? sizeof(float) * (size_t)g.splits * sd.K * sd.R * sd.S * sd.C : 0;
+    return split_ws_bytes(wgeo(cf, &sd).splits, sd.K, sd.R * sd.S * sd.C);
   }
   if (pass == 0) {
-    const Geo g = make_geo_x3(cf, s->N * s->Ho * s->Wo, s->K, s->R * s->S * s->C);
-    return g.splits > 1 ? sizeof(float) * (size_t)g.splits * g.M * g.Ncol : 0;
+    const Geo g = geo(cf, s->N * s->Ho * s->Wo, s->K, s->R * s->S * s->C);
+    return split_ws_bytes(g.splits, g.M, g.Ncol);
   }
   if (s->stride_h < 1 || s->stride_h > 2 || s->stride_w < 1 || s->stride_w > 2) return 0;
   DClass cl[4];
-  int64_t off[4];
-  int br[4], bs[4];
-  const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
+  const int n = dgrad_launch_classes(s, cl);
   size_t mx = 0;
   for (int i = 0; i < n; ++i) {
-    if (cl[i].Hc * cl[i].Wc == 0) continue;  // an empty parity class (H or W of 1) is not launched
-    const Geo g = make_geo_x3(cf, s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
-    if (g.splits > 1) mx = std::max(mx, sizeof(float) * (size_t)g.splits * g.M * g.Ncol);
+    const Geo g = geo(cf, s->N * cl[i].Hc * cl[i].Wc, s->C, (int64_t)cl[i].Rc * cl[i].Sc * s->K);
+    mx = std::max(mx, split_ws_bytes(g.splits, g.M, g.Ncol));
   }
   return mx;
+}
+extern "C" size_t mx_conv_workspace(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg) {
+  return conv_workspace(s, pass, cfg, make_geo, wgrad_geo);
+}
+extern "C" size_t mx_conv_workspace_x3(const mx_conv_shape* s, int pass, const mx_conv_cfg* cfg) {
+  return conv_workspace(s, pass, cfg, make_geo_x3, wgrad_geo_x3);
 }
 
 extern "C" int mx_conv2d_fwd_x3(const mx_conv_shape* s, const float* x, const uint16_t* w, const float* bias,
@@ -3429,13 +3455,9 @@ extern "C" int mx_conv2d_fwd_x3(const mx_conv_shape* s, const float* x, const ui
   MX_CHECK_ARG(s->K % 8 == 0 || !residual, "conv fwd x3: residual needs K %% 8 == 0");
   MX_CHECK_ARG(x && w && y, "conv fwd x3: null operand");
   ConvP p{};
-  p.src = (const uint16_t*)(const void*)x; p.wt = w;
-  p.M = s->N * s->Ho * s->Wo; p.Ncol = s->K; p.Kdim = s->R * s->S * s->C;
-  p.OH = s->Ho; p.OW = s->Wo; p.IH = s->H; p.IW = s->W; p.IC = s->C;
-  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
-  p.bias = bias; p.residual = residual; p.act = act; p.out = y; p.out_f32 = 1;
-  p.stats = stats; p.mblocks = cdiv(p.M, SROWS);
-  p.src_elems = s->N * s->H * s->W * s->C; p.wt_elems = p.Ncol * p.Kdim; p.wt_plane = p.Ncol * p.Kdim;
+  fill_fwd(p, s, x, w);
+  p.bias = bias; p.residual = residual; p.act = act; p.out = y; p.out_f32 = 1; p.stats = stats;
+  p.wt_plane = p.Ncol * p.Kdim;
   g_launch_count = 0;
   return launch_igemm_x3<0>(cf, p, make_geo_x3(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
 }
@@ -3451,6 +3473,7 @@ extern "C" int mx_conv2d_dgrad_x3(const mx_conv_shape* s, const float* dy, const
   if (rc) return rc;
   MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "conv dgrad x3: K and C must be multiples of 8");
   MX_CHECK_ARG(s->stride_h <= 2 && s->stride_w <= 2, "conv dgrad x3: strides 1 and 2 are supported");
+  const BnbArgs b{y, z, mean, invstd, act, part, part_mb};
   const bool bnb = part != nullptr;
   if (bnb) {
     MX_CHECK_ARG(s->stride_h == 1 && s->stride_w == 1, "conv dgrad x3 bnb: stride 1 only");
@@ -3458,28 +3481,12 @@ extern "C" int mx_conv2d_dgrad_x3(const mx_conv_shape* s, const float* dy, const
     MX_CHECK_ARG(part_mb == cdiv(s->N * s->H * s->W, 64), "conv dgrad x3 bnb: part rows must be cdiv(N*H*W, 64)");
   }
   DClass cl[4];
-  int64_t off[4];
-  int br[4], bs[4];
-  const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
-  const bool remap = s->stride_h > 1 || s->stride_w > 1;
-  const int64_t plane = s->C * s->R * s->S * s->K;
+  const int n = dgrad_launch_classes(s, cl);
   g_launch_count = 0;
   for (int i = 0; i < n; ++i) {
-    const DClass& c = cl[i];
-    if (c.Hc * c.Wc == 0) continue;
     ConvP p{};
-    p.src = (const uint16_t*)(const void*)dy; p.wt = wt + c.off; p.wt_plane = plane;
-    p.M = s->N * c.Hc * c.Wc; p.Ncol = s->C; p.Kdim = (int64_t)c.Rc * c.Sc * s->K;
-    p.OH = c.Hc; p.OW = c.Wc; p.IH = s->Ho; p.IW = s->Wo; p.IC = s->K;
-    p.R = std::max(c.Rc, 1); p.S = std::max(c.Sc, 1); p.st_h = 1; p.st_w = 1; p.pad_h = c.dh; p.pad_w = c.dw;
-    p.out = dx; p.out_f32 = 1; p.act = 0; p.residual = residual;
-    if (bnb) {
-      p.bnb_y = y; p.bnb_z = z; p.bnb_mean = mean; p.bnb_invstd = invstd; p.bnb_act = act; p.bnb_part = part;
-      p.bnb_mb = part_mb;
-    }
-    p.remap = remap; p.rst_h = s->stride_h; p.rst_w = s->stride_w; p.rph = c.ph; p.rpw = c.pw;
-    p.rH = s->H; p.rW = s->W;
-    p.src_elems = s->N * s->Ho * s->Wo * s->K; p.wt_elems = p.Ncol * p.Kdim;
+    fill_dgrad_class(p, s, cl[i], dy, wt, residual, dx, bnb ? &b : nullptr);
+    p.out_f32 = 1; p.wt_plane = s->C * s->R * s->S * s->K;
     rc = launch_igemm_x3<1>(cf, p, make_geo_x3(cf, p.M, p.Ncol, p.Kdim), ws, ws_bytes, (hipStream_t)stream);
     if (rc) return rc;
   }
@@ -3521,18 +3528,11 @@ extern "C" int mx_conv2d_dgrad_x3_rows(const mx_conv_shape* s, const float* dy, 
     return MX_EUNSUPPORTED;
   }
   DClass cl[4];
-  int64_t off[4];
-  int br[4], bs[4];
-  const int n = dgrad_classes(s, s->C, s->K, cl, off, br, bs);
+  const int n = dgrad_launch_classes(s, cl);
   MX_CHECK_ARG(n == 1 && cl[0].Hc == s->H && cl[0].Wc == s->W, "conv dgrad x3 rows: one stride-1 class expected");
-  const DClass& c = cl[0];
   ConvP p{};
-  p.src = (const uint16_t*)(const void*)dy; p.wt = wt + c.off; p.wt_plane = s->C * s->R * s->S * s->K;
-  p.M = s->N * c.Hc * c.Wc; p.Ncol = s->C; p.Kdim = (int64_t)c.Rc * c.Sc * s->K;
-  p.OH = c.Hc; p.OW = c.Wc; p.IH = s->Ho; p.IW = s->Wo; p.IC = s->K;
-  p.R = std::max(c.Rc, 1); p.S = std::max(c.Sc, 1); p.st_h = 1; p.st_w = 1; p.pad_h = c.dh; p.pad_w = c.dw;
-  p.out = dx; p.out_f32 = 1; p.act = 0; p.residual = residual;
-  p.src_elems = s->N * s->Ho * s->Wo * s->K; p.wt_elems = p.Ncol * p.Kdim;
+  fill_dgrad_class(p, s, cl[0], dy, wt, residual, dx, nullptr);
+  p.out_f32 = 1; p.wt_plane = s->C * s->R * s->S * s->K;
   MX_CHECK_ARG(cap >= 0 && cap <= p.M, "conv dgrad x3 rows: capacity %lld outside [0, %lld]", (long long)cap, (long long)p.M);
   MX_CHECK_ARG(p.Kdim == s->R * s->S * s->K && p.M < (1ll << 31), "conv dgrad x3 rows: unexpected class geometry");
   p.rows = rows; p.rows_count = nrows; p.rows_cap = cap;
@@ -3556,39 +3556,17 @@ extern "C" int mx_conv2d_dgrad_x3_rows(const mx_conv_shape* s, const float* dy, 
 extern "C" int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const float* x, float* dw, int64_t Kout,
                                   int64_t Cin, int layout, void* ws, size_t ws_bytes, mx_stream_t stream,
                                   const mx_conv_cfg* cfg) {
+  const char* name = "conv wgrad x3";
   Cfg cf;
   int rc = resolve_cfg(cfg, cf);
+  if (!rc) rc = wgrad_check(s, Kout, Cin, layout, name);
   if (rc) return rc;
-  rc = conv_check(s);
-  if (rc) return rc;
-  MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "conv wgrad x3: K and C must be multiples of 8");
-  MX_CHECK_ARG(Kout >= 1 && Kout <= s->K && Cin >= 1 && Cin <= s->C, "conv wgrad x3: Kout/Cin out of range");
-  MX_CHECK_ARG(layout == 0 || layout == 1, "conv wgrad x3: layout 0 (KRSC) or 1 (KCRS)");
-  MX_CHECK_ARG(s->K * s->R * s->S * s->C < (1ll << 31), "conv wgrad x3: weight too large");
   hipStream_t st = (hipStream_t)stream;
-  const int dC = (int)s->C, dRS = (int)(s->R * s->S);
-  bool dense;
-  const mx_conv_shape sd = wgrad_shape(s, &dense);
-  s = &sd;
   WgP p{};
-  p.dy = (const uint16_t*)(const void*)dy; p.x = (const uint16_t*)(const void*)x; p.dw = dw;
-  p.P = s->N * s->Ho * s->Wo; p.K = s->K; p.Ncol = s->R * s->S * s->C;
-  p.OH = s->Ho; p.OW = s->Wo; p.H = s->H; p.W = s->W; p.C = s->C; p.N = s->N;
-  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
-  p.Kout = Kout; p.Cin = Cin; p.layout = layout;
-  p.dC = dC; p.dRS = dRS;
-  const WGeo g = wgrad_geo_x3(cf, s);
-  p.kchunk = g.kchunk;
-  if (g.splits > 1) {
-    const size_t need = sizeof(float) * (size_t)g.splits * p.K * p.Ncol;
-    MX_CHECK_ARG(ws && ws_bytes >= need, "conv wgrad x3: split workspace of %zu bytes required (mx_conv_workspace_x3)",
-                 need);
-    p.slab = (float*)ws;
-  }
-  MX_CHECK_ARG(g.tiles * g.splits < (1ll << 31), "conv wgrad x3: grid too large");
-  MX_CHECK_ARG(p.P * p.K * 4 < (1ll << 31) && p.N * p.H * p.W * p.C * 4 < (1ll << 31) && p.P + 64 < (1ll << 23) &&
-                   p.N * p.H * p.W < (1ll << 23) && p.K * 4 < (1ll << 24) && p.C * 4 < (1ll << 24),
-               "conv wgrad x3: dy / x must each stay below 2 GiB and 8M pixels (32-bit / 24-bit offset math)");
+  WGeo g;
+  rc = fill_wgrad(p, g, cf, wgrad_geo_x3, s, dy, x, dw, Kout, Cin, layout, ws, ws_bytes, name, "mx_conv_workspace_x3");
+  if (!rc) rc = wgrad_x3_ranges(p, g, name);
+  if (rc) return rc;
   const bool wide = wgrad_x3_wide(cf), ww = wgrad_x3_ww(cf);
   if (ww)
     conv_wgrad_x3ww_kernel<<<(unsigned)(g.tiles * g.splits), 256, 2 * 8 * 32 * 256, st>>>(p);
@@ -3599,66 +3577,39 @@ extern "C" int mx_conv2d_wgrad_x3(const mx_conv_shape* s, const float* dy, const
   MX_LAUNCH_CHECK();
   g_launch_count = 0;
   record_launch(2, ww ? 256 : 128, (ww || wide) ? 256 : 128, g.splits, g.tiles, true, 100 + (ww ? 5 : wide ? 4 : 3));
-  if (g.splits > 1) {
-    MX_CHECK_ARG(Kout < 65536, "conv wgrad x3: too many output channels for the split reduce");
-    wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);
-    MX_LAUNCH_CHECK();
-  }
-  return MX_OK;
+  return wgrad_finish(p, g, Kout, st, name);
 }
 
 extern "C" int mx_conv2d_wgrad_x3_rows(const mx_conv_shape* s, const float* dy, const float* x, float* dw, int64_t Kout,
                                        int64_t Cin, int layout, const int32_t* tiles, const int32_t* ntiles, int64_t cap,
                                        void* ws, size_t ws_bytes, mx_stream_t stream, const mx_conv_cfg* cfg) {
+  const char* name = "conv wgrad x3 rows";
   Cfg cf;
   int rc = resolve_cfg(cfg, cf);
+  if (!rc) rc = wgrad_check(s, Kout, Cin, layout, name);
   if (rc) return rc;
-  rc = conv_check(s);
-  if (rc) return rc;
-  MX_CHECK_ARG(s->K % 8 == 0 && s->C % 8 == 0, "conv wgrad x3 rows: K and C must be multiples of 8");
-  MX_CHECK_ARG(Kout >= 1 && Kout <= s->K && Cin >= 1 && Cin <= s->C, "conv wgrad x3 rows: Kout/Cin out of range");
-  MX_CHECK_ARG(layout == 0 || layout == 1, "conv wgrad x3 rows: layout 0 (KRSC) or 1 (KCRS)");
-  MX_CHECK_ARG(s->K * s->R * s->S * s->C < (1ll << 31), "conv wgrad x3 rows: weight too large");
   MX_CHECK_ARG(dy && x && dw && tiles && ntiles, "conv wgrad x3 rows: null operand");
   MX_CHECK_ARG(!wgrad_x3_wide(cf) && !wgrad_x3_ww(cf),
                "conv wgrad x3 rows: only the 128 x 128 kernel (wgrad_variant 3) has a tile-list form");
   bool dense;
   wgrad_shape(s, &dense);
   MX_CHECK_ARG(!dense, "conv wgrad x3 rows: a dense (FC-style) conv has no pixel axis to list");
+  const int64_t ksteps = cdiv(s->N * s->Ho * s->Wo, 32);
+  MX_CHECK_ARG(cap >= 0 && cap <= ksteps, "conv wgrad x3 rows: capacity %lld outside [0, %lld]", (long long)cap,
+               (long long)ksteps);
+  // mx_conv2d_wgrad_x3's fill and geometry for the same cfg: the same splits, so the same partial sums
   WgP p{};
-  p.dy = (const uint16_t*)(const void*)dy; p.x = (const uint16_t*)(const void*)x; p.dw = dw;
-  p.P = s->N * s->Ho * s->Wo; p.K = s->K; p.Ncol = s->R * s->S * s->C;
-  p.OH = s->Ho; p.OW = s->Wo; p.H = s->H; p.W = s->W; p.C = s->C; p.N = s->N;
-  p.R = (int)s->R; p.S = (int)s->S; p.st_h = s->stride_h; p.st_w = s->stride_w; p.pad_h = s->pad_h; p.pad_w = s->pad_w;
-  p.Kout = Kout; p.Cin = Cin; p.layout = layout;
-  p.dC = (int)s->C; p.dRS = (int)(s->R * s->S);
-  MX_CHECK_ARG(cap >= 0 && cap <= cdiv(p.P, 32), "conv wgrad x3 rows: capacity %lld outside [0, %lld]", (long long)cap,
-               (long long)cdiv(p.P, 32));
-  // mx_conv2d_wgrad_x3's geometry for the same cfg: the same splits, so the same partial sums
-  const WGeo g = wgrad_geo_x3(cf, s);
-  p.kchunk = g.kchunk;
+  WGeo g;
+  rc = fill_wgrad(p, g, cf, wgrad_geo_x3, s, dy, x, dw, Kout, Cin, layout, ws, ws_bytes, name, "mx_conv_workspace_x3");
+  if (!rc) rc = wgrad_x3_ranges(p, g, name);
+  if (rc) return rc;
   p.rows = tiles; p.nrows = ntiles; p.rows_cap = cap;
-  if (g.splits > 1) {
-    const size_t need = sizeof(float) * (size_t)g.splits * p.K * p.Ncol;
-    MX_CHECK_ARG(ws && ws_bytes >= need, "conv wgrad x3 rows: split workspace of %zu bytes required (mx_conv_workspace_x3)",
-                 need);
-    p.slab = (float*)ws;
-  }
-  MX_CHECK_ARG(g.tiles * g.splits < (1ll << 31), "conv wgrad x3 rows: grid too large");
-  MX_CHECK_ARG(p.P * p.K * 4 < (1ll << 31) && p.N * p.H * p.W * p.C * 4 < (1ll << 31) && p.P + 64 < (1ll << 23) &&
-                   p.N * p.H * p.W < (1ll << 23) && p.K * 4 < (1ll << 24) && p.C * 4 < (1ll << 24),
-               "conv wgrad x3 rows: dy / x must each stay below 2 GiB and 8M pixels (32-bit / 24-bit offset math)");
   hipStream_t st = (hipStream_t)stream;
   conv_wgrad_x3_rows_kernel<<<(unsigned)(g.tiles * g.splits), NT, 2 * 4 * 32 * 256, st>>>(p);
   MX_LAUNCH_CHECK();
   g_launch_count = 0;
   record_launch(2, 128, 128, g.splits, g.tiles, true, 106);
-  if (g.splits > 1) {
-    MX_CHECK_ARG(Kout < 65536, "conv wgrad x3 rows: too many output channels for the split reduce");
-    wgrad_reduce_kernel<<<dim3((unsigned)cdiv(p.Ncol / 4, 64), (unsigned)Kout), 256, 0, st>>>(p, (int)g.splits);
-    MX_LAUNCH_CHECK();
-  }
-  return MX_OK;
+  return wgrad_finish(p, g, Kout, st, name);
 }
 
 extern "C" int mx_conv2d_stem_x3(const mx_conv_shape* s, const float* x, const uint16_t* w, const float* bias,
