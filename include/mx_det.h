@@ -240,6 +240,43 @@ int mx_det_candidates(const float* logits, int64_t ldl, const float* reg, int64_
 int mx_det_select(const int64_t* keep, const int64_t* num_keep, const float* boxes, const float* scores,
                   const int64_t* labels, const int32_t* grp, int64_t n, int64_t N, int64_t D, const float* ratios,
                   float* out_boxes, float* out_scores, int64_t* out_labels, int32_t* counts, mx_stream_t stream);
+/* Test-time augmentation: V views of each of N images through the model, their detection sets fused
+ * by box voting (Gidaris & Komodakis 2015; Detectron's bbox_vote). The box head ran on V*N*P rows
+ * ordered view-major, then image, then row, and mx_det_candidates was called with N' = V*N, so slot
+ *   t = ((v*N + i)*P + r)*(C-1) + (c-1),  n = V*N*P*(C-1),  a live slot has grp[t] == v*N + i.
+ * Both entries check n == V*N*P*(C-1) < 2^30, 1 <= V <= 64, 2 <= C <= 1024. Stream-ordered chain:
+ *   mx_det_candidates(N' = V*N) -> mx_det_views_fold -> mx_batched_nms_grouped(G = N) -> mx_det_select_vote */
+/* One elementwise launch that brings every view's candidates into the image's own frame and group.
+ * For slot t of block b = v*N + i:
+ *   grp[t] == b (live): grp_out[t] = i; when flip_host[v] != 0 (int32 [V] on the host), the box is
+ *     mirrored in continuous coordinates as torchvision's horizontal flip maps boxes: x1' = w - x2,
+ *     x2' = w - x1 with w = hw[i][1] (hw [N][2] f32 (h, w), the resized sizes), one f32 subtraction
+ *     each, y unchanged; candidates are clamped to [0, w], so 0 <= x1' <= x2' <= w;
+ *   any other grp[t] (dead): grp_out[t] = N and the box is copied unchanged.
+ * Every element of both outputs is written; boxes_out == boxes and grp_out == grp are allowed.
+ * n == 0 launches nothing. */
+int mx_det_views_fold(const float* boxes, const int32_t* grp, const float* hw, int64_t n, int64_t V, int64_t N,
+                      int64_t P, int64_t C, const int32_t* flip_host, float* boxes_out, int32_t* grp_out,
+                      mx_stream_t stream);
+/* mx_det_select on the folded candidates (outputs, counts, zeros past the count, -1 counts when
+ * num_keep < 0, n == 0, ratios: all as there) with each selected survivor's box replaced by the
+ * score-weighted mean of its voters, in one launch. For survivor k of image g with label c
+ * (1 <= c < C), the voters are the slots t = ((v*N + g)*P + r)*(C-1) + (c-1), v = 0..V-1,
+ * r = 0..P-1, with grp[t] == g and iou(box_k, box_t) >= vote_iou (false on NaN), where
+ *   iou = inter / ((area_k + area_t) - inter), area = (x2 - x1)*(y2 - y1),
+ *   inter = max(min(x2) - max(x1), 0) * max(min(y2) - max(y1), 0)
+ * is torchvision's box_iou in f32, every operation rounded once, and vote_iou is rounded to f32 once.
+ * Per coordinate the voted value is (float)(sum_t (double)s_t*(double)b_t / sum_t (double)s_t): both
+ * sums f64, added in ascending slot order with one rounding per add (each f32 x f32 product is exact
+ * in f64), one f64 division, one rounding to f32 -- independent of the launch geometry. A survivor
+ * whose only voter is itself keeps its box bit for bit; a voted coordinate lies within its voters'
+ * minimum and maximum. A survivor with no voter at all (or a label outside [1, C)) keeps its box.
+ * The box is then multiplied once by rw / rh as in mx_det_select; score and label are the survivor's.
+ * vote_iou > 1 or NaN: no voting, the output is bitwise mx_det_select's. */
+int mx_det_select_vote(const int64_t* keep, const int64_t* num_keep, const float* boxes, const float* scores,
+                       const int64_t* labels, const int32_t* grp, int64_t n, int64_t V, int64_t N, int64_t P,
+                       int64_t C, int64_t D, double vote_iou, const float* ratios, float* out_boxes,
+                       float* out_scores, int64_t* out_labels, int32_t* counts, mx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Corruption augmentation (scripts/augmentations.py:14-56, RandomCorruption :60-74), uint8 HWC.

@@ -125,6 +125,145 @@ det_select_kernel(const int64_t* __restrict__ keep, const int64_t* __restrict__ 
   }
 }
 
+// ---- test-time augmentation: several views of each image fused by box voting ------------------
+// Candidates of V views x N images (mx_det_candidates over V*N "images", P rows per block): slot
+// t = ((v*N + i)*P + r)*(C-1) + (c-1). The fold brings every live slot into image i's frame and
+// image group i; the voting select replaces each selected NMS survivor by the score-weighted mean
+// of the candidates of its image and class that overlap it (Gidaris & Komodakis 2015).
+
+// One thread per slot; per = P*(C-1) slots per (view, image) block. flips: bit v set = view v is
+// mirrored horizontally. Reads its slot before it writes it, so out == in is fine.
+__global__ void __launch_bounds__(DET_T)
+det_views_fold_kernel(const float4* boxes, const int32_t* grp, const float* __restrict__ hw,
+                      int64_t n, int64_t per, int N, uint64_t flips, float4* boxes_out, int32_t* grp_out) {
+  const int64_t t = (int64_t)blockIdx.x * DET_T + threadIdx.x;
+  if (t >= n) return;
+  const int64_t b = t / per;
+  const int v = (int)(b / N), i = (int)(b % N);
+  float4 bx = boxes[t];
+  const bool live = grp[t] == (int32_t)b;
+  if (live && ((flips >> v) & 1)) {
+    const float w = hw[2 * i + 1];
+    bx = make_float4(w - bx.z, bx.y, w - bx.x, bx.w);
+  }
+  boxes_out[t] = bx;
+  grp_out[t] = live ? i : N;
+}
+
+// torchvision box_iou of one pair in f32 (iou_tv of mx_match.hip): every operation rounds once
+__device__ __forceinline__ float det_area(float4 b) { return (b.z - b.x) * (b.w - b.y); }
+__device__ __forceinline__ float det_iou(float4 a, float area_a, float4 b, float area_b) {
+  const float ltx = fmaxf(a.x, b.x), lty = fmaxf(a.y, b.y);
+  const float rbx = fminf(a.z, b.z), rby = fminf(a.w, b.w);
+  float w = rbx - ltx, h = rby - lty;
+  w = w < 0.f ? 0.f : w;
+  h = h < 0.f ? 0.f : h;
+  const float inter = w * h;
+  return inter / ((area_a + area_b) - inter);
+}
+
+constexpr int VOTE_PER = DET_ROWS;  // output slots per block: one wave each
+
+// Block (g, part) owns the output slots d = part*VOTE_PER + wave of image g; every block redoes the
+// two searches of det_select_kernel (lanes 0 of waves 0 and 1, side by side). A wave with a survivor
+// walks the V*P slots of its image and class in ascending slot order, 64 per round: the lanes test
+// one candidate each, a ballot collects the voters, and every lane adds them in ascending bit order
+// from broadcast values -- one f64 accumulation chain per sum, whatever the launch geometry. The
+// next round's loads are issued before the current round's voters are added.
+__global__ void __launch_bounds__(DET_T)
+det_select_vote_kernel(const int64_t* __restrict__ keep, const int64_t* __restrict__ num_keep,
+                       const float4* __restrict__ boxes, const float* __restrict__ scores,
+                       const int64_t* __restrict__ labels, const int32_t* __restrict__ grp, int64_t n, int V, int N,
+                       int P, int C, int D, int parts, bool vote, float vote_iou, const float* __restrict__ ratios,
+                       float4* __restrict__ out_boxes, float* __restrict__ out_scores,
+                       int64_t* __restrict__ out_labels, int32_t* __restrict__ counts) {
+  __shared__ int64_t bound_s[2];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int g = blockIdx.x / parts, part = blockIdx.x % parts;
+  int64_t nk = *num_keep;
+  const bool failed = nk < 0;
+  nk = nk < 0 ? 0 : (nk > n ? n : nk);
+  if (lane == 0 && wv < 2) bound_s[wv] = det_lower_bound(keep, grp, nk, n, g + wv);
+  __syncthreads();
+  const int64_t lo = bound_s[0], hi = bound_s[1];
+  const int cnt = (int)(hi - lo < D ? hi - lo : D);
+  if (part == 0 && threadIdx.x == 0) counts[g] = failed ? -1 : cnt;
+  const int d = part * VOTE_PER + wv;  // wave-uniform
+  if (d >= D) return;
+  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+  float s = 0.f;
+  int64_t l = 0;
+  if (d < cnt) {
+    const int64_t k = keep[lo + d];  // in [0, n): the search saw it as image g
+    b = boxes[k];
+    s = scores[k];
+    l = labels[k];
+    if (vote && l >= 1 && l < C) {
+      const float area_k = det_area(b);
+      const int VP = V * P;  // <= n < 2^30
+      // candidate j = v*P + r of this image and class: slot ((v*N + g)*P + r)*(C-1) + (l-1) < n
+      auto slot = [&](int j) { return (((int64_t)(j / P) * N + g) * P + j % P) * (C - 1) + (l - 1); };
+      float4 cb = make_float4(0.f, 0.f, 0.f, 0.f);
+      float cs = 0.f;
+      bool cl = false;
+      if (lane < VP) {
+        const int64_t t = slot(lane);
+        cl = grp[t] == g;
+        cb = boxes[t];
+        cs = scores[t];
+      }
+      double ss = 0.0, sx1 = 0.0, sy1 = 0.0, sx2 = 0.0, sy2 = 0.0;
+      bool any = false;
+      for (int j0 = 0; j0 < VP; j0 += 64) {
+        float4 nb = make_float4(0.f, 0.f, 0.f, 0.f);
+        float ns = 0.f;
+        bool nl = false;
+        if (j0 + 64 + lane < VP) {
+          const int64_t t = slot(j0 + 64 + lane);
+          nl = grp[t] == g;
+          nb = boxes[t];
+          ns = scores[t];
+        }
+        // false on NaN: a NaN IoU never votes
+        uint64_t hits = __ballot(cl && det_iou(b, area_k, cb, det_area(cb)) >= vote_iou);
+        any |= hits != 0;
+        while (hits) {
+          const int src = __ffsll((unsigned long long)hits) - 1;
+          hits &= hits - 1;
+          const double w = (double)__shfl(cs, src);
+          ss = ss + w;
+          sx1 = sx1 + w * (double)__shfl(cb.x, src);  // f32 x f32 is exact in f64
+          sy1 = sy1 + w * (double)__shfl(cb.y, src);
+          sx2 = sx2 + w * (double)__shfl(cb.z, src);
+          sy2 = sy2 + w * (double)__shfl(cb.w, src);
+        }
+        cb = nb;
+        cs = ns;
+        cl = nl;
+      }
+      if (any) b = make_float4((float)(sx1 / ss), (float)(sy1 / ss), (float)(sx2 / ss), (float)(sy2 / ss));
+    }
+    if (ratios) {
+      const float rh = ratios[2 * g], rw = ratios[2 * g + 1];
+      b = make_float4(b.x * rw, b.y * rh, b.z * rw, b.w * rh);
+    }
+  }
+  if (lane == 0) {
+    const int64_t o = (int64_t)g * D + d;
+    out_boxes[o] = b;
+    out_scores[o] = s;
+    out_labels[o] = l;
+  }
+}
+
+// n == V*N*P*(C-1) < 2^30 without overflow on the way
+static bool det_views_sizes(int64_t n, int64_t V, int64_t N, int64_t P, int64_t C) {
+  if (!(V >= 1 && V <= 64 && N >= 1 && N < (1ll << 31) && P >= 0 && P < (1ll << 30) && C >= 2 && C <= DET_CMAX))
+    return false;
+  if (P && V * N > (1ll << 30) / P) return false;  // V*N < 2^37: no overflow here or below
+  return V * N * P * (C - 1) == n && n < (1ll << 30);
+}
+
 }  // namespace mx
 
 using namespace mx;
@@ -162,6 +301,45 @@ extern "C" int mx_det_select(const int64_t* keep, const int64_t* num_keep, const
   det_select_kernel<<<(unsigned)N, DET_T, 0, (hipStream_t)stream>>>(keep, num_keep, (const float4*)boxes, scores, labels,
                                                                      grp, n, (int)D, ratios, (float4*)out_boxes,
                                                                      out_scores, out_labels, counts);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+extern "C" int mx_det_views_fold(const float* boxes, const int32_t* grp, const float* hw, int64_t n, int64_t V,
+                                 int64_t N, int64_t P, int64_t C, const int32_t* flip_host, float* boxes_out,
+                                 int32_t* grp_out, mx_stream_t stream) {
+  MX_CHECK_ARG(det_views_sizes(n, V, N, P, C),
+               "mx_det_views_fold: bad sizes n=%lld (= V*N*P*(C-1) < 2^30) V=%lld (1..64) N=%lld P=%lld C=%lld (2..%d)",
+               (long long)n, (long long)V, (long long)N, (long long)P, (long long)C, DET_CMAX);
+  MX_CHECK_ARG(flip_host, "mx_det_views_fold: null flip flags");
+  if (n == 0) return MX_OK;
+  MX_CHECK_ARG(boxes && grp && hw && boxes_out && grp_out, "mx_det_views_fold: null pointer");
+  uint64_t flips = 0;
+  for (int v = 0; v < V; ++v) flips |= (uint64_t)(flip_host[v] != 0) << v;
+  det_views_fold_kernel<<<(unsigned)cdiv(n, DET_T), DET_T, 0, (hipStream_t)stream>>>(
+      (const float4*)boxes, grp, hw, n, P * (C - 1), (int)N, flips, (float4*)boxes_out, grp_out);
+  MX_LAUNCH_CHECK();
+  return MX_OK;
+}
+
+extern "C" int mx_det_select_vote(const int64_t* keep, const int64_t* num_keep, const float* boxes, const float* scores,
+                                  const int64_t* labels, const int32_t* grp, int64_t n, int64_t V, int64_t N, int64_t P,
+                                  int64_t C, int64_t D, double vote_iou, const float* ratios, float* out_boxes,
+                                  float* out_scores, int64_t* out_labels, int32_t* counts, mx_stream_t stream) {
+  MX_CHECK_ARG(det_views_sizes(n, V, N, P, C) && D >= 1 && D < (1ll << 24),
+               "mx_det_select_vote: bad sizes n=%lld (= V*N*P*(C-1) < 2^30) V=%lld (1..64) N=%lld P=%lld C=%lld (2..%d) "
+               "D=%lld",
+               (long long)n, (long long)V, (long long)N, (long long)P, (long long)C, DET_CMAX, (long long)D);
+  const int64_t parts = cdiv(D, VOTE_PER);
+  MX_CHECK_ARG(N * parts < (1ll << 31), "mx_det_select_vote: N=%lld x D=%lld too large for one launch", (long long)N,
+               (long long)D);
+  MX_CHECK_ARG(num_keep && out_boxes && out_scores && out_labels && counts &&
+                   (n == 0 || (keep && boxes && scores && labels && grp)),
+               "mx_det_select_vote: null pointer");
+  const float thr = (float)vote_iou;  // rounded once; > 1 or NaN: no voting, mx_det_select's result
+  det_select_vote_kernel<<<(unsigned)(N * parts), DET_T, 0, (hipStream_t)stream>>>(
+      keep, num_keep, (const float4*)boxes, scores, labels, grp, n, (int)V, (int)N, (int)P, (int)C, (int)D, (int)parts,
+      thr <= 1.f, thr, ratios, (float4*)out_boxes, out_scores, out_labels, counts);
   MX_LAUNCH_CHECK();
   return MX_OK;
 }

@@ -119,6 +119,9 @@ _SIGS = {
                                   c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mx_det_select": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp,
                               c_vp]),
+    "mx_det_views_fold": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mx_det_select_vote": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_d,
+                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mx_corrupt_u8": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_f, c_u64, c_vp, c_d, c_vp, c_vp, c_vp]),
     "mx_filter2d_u8": (c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_vp, c_vp]),
     "mx_corrupt_batch_u8": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),

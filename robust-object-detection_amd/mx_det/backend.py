@@ -193,6 +193,14 @@ class HipBackend:
         return ops.detections_postprocess(logits, reg, rois, img, hw, N, score_thresh, nms_thresh, detections_per_img,
                                           ratios, weights, max_seg)
 
+    def detections_postprocess_views(self, logits, reg, rois, img, hw, N, V, flips, score_thresh, nms_thresh,
+                                     detections_per_img, vote_iou, ratios=None, weights=ops.ROI_WEIGHTS, max_seg=None):
+        """detections_postprocess over V views of each of the N images (mx_det.tta): every view's candidates
+        folded into the image's frame, one class-wise NMS per image over all views, box voting on the
+        survivors; the same padded outputs, no host synchronisation."""
+        return ops.detections_postprocess_views(logits, reg, rois, img, hw, N, V, flips, score_thresh, nms_thresh,
+                                                detections_per_img, vote_iou, ratios, weights, max_seg)
+
     def anchors_level(self, size, ratios, gh, gw, sh, sw, device):
         return ops.anchors_level(size, ratios, gh, gw, sh, sw, device)
 

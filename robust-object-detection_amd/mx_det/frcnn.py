@@ -856,24 +856,36 @@ class RoIHeads(nn.Module):
             c = cache[key] = (bi.to(torch.float32)[:, None], bi, hw.to(dev), ratios.to(dev))
         return c
 
-    def _detect_fused(self, feats, proposals, image_sizes, original_sizes, be):
+    def _detect_fused(self, feats, proposals, image_sizes, original_sizes, be, tta=None):
         """The eval tail without per-image host work: the box head on the static N * post padded proposal
         rows (a padded row keeps its image's index for RoIAlign and is dead, img = N, for the candidate
         kernel), then softmax, decode, clip, filters, class-wise NMS, top detections_per_img and the
         rescale to the original sizes on the device (be.detections_postprocess); one host sync per batch
-        reads the per-image counts."""
+        reads the per-image counts. tta: the V * N proposal blocks are V views of N images, view-major; the
+        views' candidates are fused per image (be.detections_postprocess_views) with the sizes and ratios
+        of the N images."""
         pb, _, pvalid = proposals
         N, post = pvalid.shape
         dev = pb.device
+        V = len(tta.views) if tta is not None else 1
+        if original_sizes is not None and V > 1:
+            original_sizes = list(original_sizes) * V
         bcol, bi, hw, ratios = self._det_consts(N, post, image_sizes, original_sizes, dev)
         boxes = pb.reshape(-1, 4)
         scales, k_min = self._scales(feats, image_sizes)
         x = be.multiscale_roi_align(feats, torch.cat([bcol, boxes], 1), scales, k_min)
         class_logits, box_regression = self.box_predictor(self.box_head(x, be), be)
         img = torch.where(pvalid.reshape(-1), bi, N)
-        ob, osc, ol, counts = be.detections_postprocess(class_logits, box_regression, boxes, img, hw, N,
-                                                        self.score_thresh, self.nms_thresh, self.detections_per_img,
-                                                        ratios=ratios, weights=ROI_WEIGHTS, max_seg=max(post, 1000))
+        if tta is not None:
+            N //= V
+            ob, osc, ol, counts = be.detections_postprocess_views(
+                class_logits, box_regression, boxes, img, hw[:N], N, V, tta.flips, self.score_thresh, self.nms_thresh,
+                self.detections_per_img, tta.vote_iou, ratios=ratios[:N], weights=ROI_WEIGHTS, max_seg=post)
+        else:
+            ob, osc, ol, counts = be.detections_postprocess(class_logits, box_regression, boxes, img, hw, N,
+                                                            self.score_thresh, self.nms_thresh,
+                                                            self.detections_per_img, ratios=ratios, weights=ROI_WEIGHTS,
+                                                            max_seg=max(post, 1000))
         counts = counts.tolist()  # the tail's one host sync
         if any(c < 0 for c in counts):
             raise RuntimeError("detection NMS: a class segment exceeded max_seg (num_keep < 0)")
@@ -929,14 +941,16 @@ class RoIHeads(nn.Module):
         sm = (pos_m | neg_m).flatten()
         return box_p, lab_p, tg_p, sm, sm.sum()
 
-    def forward(self, features, proposals, image_sizes, targets=None, be=None, sampled=None, original_sizes=None):
+    def forward(self, features, proposals, image_sizes, targets=None, be=None, sampled=None, original_sizes=None,
+                tta=None):
         """sampled: the sample() outputs with the sampled count already on the host (FasterRCNN's
         captured proposal stage), in place of matching and sampling here. Eval with padded proposals
-        (a (boxes, scores, valid) tuple, fused_active): detections already scaled to original_sizes."""
+        (a (boxes, scores, valid) tuple, fused_active): detections already scaled to original_sizes. tta (an
+        mx_det.tta.TTA): the proposals and image_sizes hold len(tta.views) blocks of the images, view-major."""
         feats = [features[k] for k in self.featmap_names]
         dev = feats[0].device
         if not self.training and isinstance(proposals, tuple):
-            return self._detect_fused(feats, proposals, image_sizes, original_sizes, be), {}
+            return self._detect_fused(feats, proposals, image_sizes, original_sizes, be, tta), {}
         if self.training and sampled is not None:
             box_p, lab_p, tg_p, sm, total = sampled
             cm = lab_p.shape[1]
@@ -1162,6 +1176,7 @@ class FasterRCNN(nn.Module):
         box_head = box_head or FastRCNNConvFCHead()
         self.roi_heads = RoIHeads(box_head, FastRCNNPredictor(1024, num_classes))
         self._be = kw.get("backend")
+        self.tta = None  # an mx_det.tta.TTA: eval forwards run every image and its mirror, fused by box voting
 
     @property
     def be(self):
@@ -1170,6 +1185,24 @@ class FasterRCNN(nn.Module):
     def set_backend(self, be):
         self._be = be
         return self
+
+    def _tta_views(self, be):
+        """self.tta when this forward is a test-time-augmented one (eval mode, tta set), else None. Refused
+        on a backend without the fused views tail and beside an enabled BNAdapter (what an "image" is for
+        the adapter's prior when every image arrives twice is undecided)."""
+        tta = self.__dict__.get("tta")
+        if tta is None or self.training:
+            return None
+        if not hasattr(be, "detections_postprocess_views"):
+            raise NotImplementedError(f"backend {getattr(be, 'name', type(be).__name__)!r} has no test-time "
+                                      "augmentation (detections_postprocess_views is a chain of HIP kernels)")
+        bns = self.__dict__.get("_mx_bns")
+        if bns is None:
+            bns = [m for m in self.modules() if isinstance(m, mc.BatchNorm2d)]
+        if any(mc.bn_adapting(b) is not None for b in bns):
+            raise ValueError("test-time augmentation (model.tta) cannot be combined with an enabled BNAdapter: "
+                             "disable one of them")
+        return tta
 
     def _trunk(self, x, be):
         """Backbone + FPN + RPN-head convs as one captured HIP graph per input shape (training, HIP
@@ -1277,6 +1310,13 @@ class FasterRCNN(nn.Module):
         else:  # float CHW (reference ToDtype output) or uint8 HWC tensors
             original = [(int(im.shape[0]), int(im.shape[1])) if im.dtype == torch.uint8 else
                         (int(im.shape[-2]), int(im.shape[-1])) for im in images]
+        tta = self._tta_views(be)
+        if tta is not None:  # [I_0 .. I_{N-1}, flip(I_0) .. flip(I_{N-1})]: view-major, `original` keeps N entries
+            if isinstance(images, torch.Tensor):
+                images = torch.cat([images] + [images.flip(2) for f in tta.flips if f])
+            else:  # W is axis 1 of a uint8 HWC frame, the last axis of a float CHW tensor
+                images = list(images) + [im.flip(1 if im.dtype == torch.uint8 else -1)
+                                         for f in tta.flips if f for im in images]
         if self.training and dev_boxes:
             # one check launch + the pinned copy on the HIP backend (else the torch compares), issued
             # ahead of the trunk: two launches of host time before the step's first kernels, and the
@@ -1294,7 +1334,8 @@ class FasterRCNN(nn.Module):
         # measured 0.5 % slower than issuing them while the trunk runs (A/B on one box), so off
         defer = os.environ.get("MX_RPN_DEFER_LOSSES", "0") != "0"
         stage = self._stage(il, features, head, targets, be) if not defer else None
-        fused = self.roi_heads.fused_active(be)  # eval: the whole detection tail on the device
+        # eval: the whole detection tail on the device (always under test-time augmentation)
+        fused = tta is not None or self.roi_heads.fused_active(be)
         try:
             if stage is not None:  # HIP-graph replay of the proposal stage (no autograd inside)
                 objectness, pred_deltas = head[0], head[1]
@@ -1320,7 +1361,7 @@ class FasterRCNN(nn.Module):
             if gt_ready is not None:  # the RoI sampler reads the GT batch the RPN's side stream built
                 torch.cuda.current_stream().wait_event(gt_ready)
             detections, det_losses = self.roi_heads(features, proposals, il.image_sizes, targets, be, sampled=sampled,
-                                                    original_sizes=original)
+                                                    original_sizes=original, tta=tta)
             self.rpn.check_nms()
             mc.rows_check()  # the RPN head's row lists of the previous backward (conv.RowLists)
         finally:  # also when the step raises: no side-stream work is left unjoined behind it

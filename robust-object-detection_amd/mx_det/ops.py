@@ -643,6 +643,77 @@ def detections_postprocess(logits, reg, rois, img, hw, N, score_thresh, nms_thre
     return detection_select(keep, nk, boxes, scores, labels, grp, N, detections_per_img, ratios)
 
 
+def detection_views_fold(boxes, grp, hw, V, N, P, C, flips, inplace=False):
+    """Candidates of V views x N images (detection_candidates over V * N images, P rows per (view, image)
+    block: slot ((v * N + i) * P + r) * (C - 1) + (c - 1)) brought into image i's frame and group
+    (mx_det_views_fold): a live slot (grp == v * N + i) gets grp i and, where flips[v], the mirrored
+    box (w - x2, y1, w - x1, y2) with w = hw[i, 1]; any other slot gets grp N and keeps its box. hw [N, 2].
+    -> (boxes [n, 4], grp [n] int32); inplace=True writes into the inputs. No host synchronisation."""
+    _dev(boxes, grp, hw)
+    V, N, P, C = int(V), int(N), int(P), int(C)
+    n = V * N * P * (C - 1)
+    _check(boxes.shape == (n, 4) and grp.shape == (n,) and hw.shape == (N, 2),
+           "detection_views_fold: boxes [n, 4], grp [n], hw [N, 2] with n = V * N * P * (C - 1)")
+    _check(boxes.dtype == torch.float32 and grp.dtype == torch.int32 and boxes.is_contiguous() and grp.is_contiguous(),
+           "detection_views_fold: contiguous f32 boxes and int32 grp")
+    _check(len(flips) == V, "detection_views_fold: one flip flag per view")
+    ob, og = (boxes, grp) if inplace else (torch.empty_like(boxes), torch.empty_like(grp))
+    call("mx_det_views_fold", _p(boxes), _p(grp), _p(hw.float().contiguous()), n, V, N, P, C,
+         (ctypes.c_int32 * V)(*[int(bool(f)) for f in flips]), _p(ob), _p(og), _stream())
+    return ob, og
+
+
+def detection_select_vote(keep, num_keep, boxes, scores, labels, grp, V, N, P, C, detections_per_img, vote_iou,
+                          ratios=None):
+    """detection_select on folded candidates with box voting (mx_det_select_vote): each selected survivor's
+    box becomes the score-weighted mean (f64 sums in ascending slot order) of the candidates of its image
+    and class, over all V views, whose f32 IoU with it is >= vote_iou; score and label stay the
+    survivor's. vote_iou > 1 or NaN: no voting, detection_select's result. Same outputs as
+    detection_select. No host synchronisation."""
+    _dev(keep, num_keep, boxes, scores, labels, grp)
+    V, N, P, C, D = int(V), int(N), int(P), int(C), int(detections_per_img)
+    n = scores.shape[0]
+    _check(n == V * N * P * (C - 1), "detection_select_vote: n = V * N * P * (C - 1)")
+    _check(boxes.shape == (n, 4) and labels.shape == (n,) and grp.shape == (n,) and keep.shape[0] >= n,
+           "detection_select_vote: shapes")
+    _check(D >= 1, "detection_select_vote: detections_per_img >= 1")
+    _check(keep.dtype == torch.int64 and num_keep.dtype == torch.int64 and labels.dtype == torch.int64
+           and grp.dtype == torch.int32, "detection_select_vote: keep / num_keep / labels int64, grp int32")
+    _check(ratios is None or (ratios.is_cuda and ratios.shape == (N, 2)),
+           "detection_select_vote: ratios [N, 2] on the device")
+    dev = scores.device
+    ob = torch.empty((N, D, 4), dtype=torch.float32, device=dev)
+    os_ = torch.empty((N, D), dtype=torch.float32, device=dev)
+    ol = torch.empty((N, D), dtype=torch.int64, device=dev)
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    rt = ratios.float().contiguous() if ratios is not None else None
+    call("mx_det_select_vote", _p(keep.contiguous()), _p(num_keep), _p(boxes.float().contiguous()),
+         _p(scores.float().contiguous()), _p(labels.contiguous()), _p(grp.contiguous()), n, V, N, P, C, D,
+         float(vote_iou), _p(rt), _p(ob), _p(os_), _p(ol), _p(counts), _stream())
+    return ob, os_, ol, counts
+
+
+def detections_postprocess_views(logits, reg, rois, img, hw, N, V, flips, score_thresh, nms_thresh, detections_per_img,
+                                 vote_iou, ratios=None, weights=ROI_WEIGHTS, max_seg=None):
+    """detections_postprocess over V views of N images, fused by box voting: logits / reg / rois / img
+    hold V * N blocks of P rows (view-major, then image; img in [0, V * N) or dead), hw [N, 2] and ratios
+    [N, 2] belong to the N images. detection_candidates over V * N images (hw tiled per view) ->
+    detection_views_fold -> batched_nms_grouped by label with G = N (an image's segment now holds the
+    rows of every view: max_seg = V * max(P, 1000), or V * max_seg when given per view) ->
+    detection_select_vote. Same outputs as detections_postprocess. No host synchronisation."""
+    R, C = logits.shape
+    V, N = int(V), int(N)
+    _check(V >= 1 and N >= 1 and R % (V * N) == 0, "detections_postprocess_views: R = V * N * P rows")
+    _check(hw.shape == (N, 2), "detections_postprocess_views: hw [N, 2] of the N images")
+    P = R // (V * N)
+    scores, boxes, labels, grp = detection_candidates(logits, reg, rois, img, hw.repeat(V, 1), V * N, score_thresh,
+                                                      weights=weights)
+    boxes, grp = detection_views_fold(boxes, grp, hw, V, N, P, C, flips, inplace=True)
+    ms = V * max(int(max_seg) if max_seg else P, 1000)
+    keep, nk = batched_nms_grouped(boxes, scores, labels, grp, N, C, nms_thresh, ms)
+    return detection_select_vote(keep, nk, boxes, scores, labels, grp, V, N, P, C, detections_per_img, vote_iou, ratios)
+
+
 # ---------------------------------------------------------------------------------------------
 CORRUPT_NONE, CORRUPT_NOISE, CORRUPT_BLUR, CORRUPT_LOWRES = 0, 1, 2, 3
 CORRUPT_JPEG = 4  # not an mx_corrupt_u8 op: corrupt_u8 hands these images to mx_corrupt_jpeg_u8

@@ -12,6 +12,9 @@ MX_BN_ADAPT=<mode>[:<prior>] (batch or stream; prior in images, default 16; unse
 checkpoint a second time under test-time BatchNorm adaptation (mx_det.adapt) and adds it as
 <name>_BNAdapt next to the unadapted entry, in the same schema; MX_BN_ADAPT_FREEZE_AFTER=<images>
 freezes the stream-mode statistics after that many images of each variant.
+MX_TTA=flip[:<vote_iou>] (default 0.8; unset: off) evaluates every checkpoint once more under flip test-time
+augmentation with box voting (mx_det.tta) and adds it as <name>_TTA, in the same schema; the plain and the
+_BNAdapt passes of the same run stay single-view.
 """
 import csv
 import json
@@ -22,6 +25,7 @@ from pathlib import Path
 import torch
 
 from mx_det import adapt as bn_adapt
+from mx_det import tta as mx_tta
 from mx_det.augment import EXTRA_VARIANTS, env_extra_variants, severity_variants
 from mx_det.engine import dist_info, eval_frcnn_variant, init_device, load_frcnn_checkpoint
 
@@ -56,19 +60,24 @@ def variant_paths(root, v):
 
 
 ADAPT_SUFFIX = "_BNAdapt"
+TTA_SUFFIX = "_TTA"
 
 
-def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None, restore_clean=False, counts=None, adapt=None):
+def eval_model(name, ckpt, dev, root=None, restorer=None, variants=None, restore_clean=False, counts=None, adapt=None,
+               tta=None):
     """restore_clean: apply `restorer` to Test_Clean as well (a blind mx_det.gate.GatedRestorer decides per
     image, so the directory name no longer does). counts: a dict that receives the restorer's
     take_counts() per variant (this rank's shard). adapt: (mode, prior) of a mx_det.adapt.BNAdapter for the
-    model, reset at the start of every variant (None: the running statistics, as the reference)."""
+    model, reset at the start of every variant (None: the running statistics, as the reference). tta: an
+    mx_det.tta.TTA the model evaluates under (None: one view)."""
     rank = dist_info()[1]
     root = COCO_TESTSET_ROOT if root is None else root
     variants = all_variants() if variants is None else variants
     if rank == 0:
         print("=" * 60 + f"\n  {name}  (COCOeval bbox)\n" + "=" * 60, flush=True)
     model = load_frcnn_checkpoint(ckpt, dev)
+    if tta is not None:
+        model.tta = tta
     kw = {} if adapt is None else dict(adapter=bn_adapt.BNAdapter(model, mode=adapt[0], prior=adapt[1]))
     res = {}
     for v in variants:
@@ -94,7 +103,8 @@ def save_json(all_results, path):
 def save_csv(all_results, path, variants=None, pairs=None):
     variants = all_variants() if variants is None else variants
     pairs = BASELINE_PAIRS if pairs is None else pairs
-    models = [m for base in MODEL_ORDER for m in (base, base + ADAPT_SUFFIX) if m in all_results]
+    models = [m for base in MODEL_ORDER for m in (base, base + ADAPT_SUFFIX, base + TTA_SUFFIX)
+              if m in all_results]
     with open(path, "w", newline="", encoding="utf-8") as f:
         w = csv.writer(f)
         w.writerow(["Model", "Metric"] + [short(v) for v in variants])
@@ -119,6 +129,7 @@ def save_csv(all_results, path, variants=None, pairs=None):
 def main():
     dev, world, rank = init_device()
     adapt = bn_adapt.parse_env(os.environ.get("MX_BN_ADAPT", ""))  # a bad value raises before any model loads
+    tta = mx_tta.parse_env(os.environ.get("MX_TTA", ""))  # likewise
     t0 = time.time()
     all_results = {}
     for name, ck in CKPTS.items():
@@ -129,6 +140,10 @@ def main():
             r = eval_model(name + ADAPT_SUFFIX, ck, dev, adapt=adapt)
             if rank == 0:
                 all_results[name + ADAPT_SUFFIX] = r
+        if tta is not None:
+            r = eval_model(name + TTA_SUFFIX, ck, dev, tta=tta)
+            if rank == 0:
+                all_results[name + TTA_SUFFIX] = r
     if rank == 0:
         print("\n  RT-DETR-L / YOLOv8m: Ultralytics branches not part of this build (skipped)")
         print(f"\nTotal evaluation time: {(time.time() - t0) / 60:.1f} min")
