@@ -363,6 +363,85 @@ typedef struct mx_weather_desc {
 int mx_weather_batch_u8(const mx_weather_desc* descs_host, int64_t n, const float* noise, mx_stream_t stream);
 /* out[0], out[1] = rows, columns of the output tile one workgroup of mx_weather_batch_u8 owns. */
 int mx_weather_batch_tile(int32_t out[2]);
+
+/* ---------------------------------------------------------------------------------------------
+ * Detection overlays and side-by-side panels (csrc/mx_draw.hip): what scripts/demo_inference.py draws
+ * with cv2 in the reference (draw_boxes, add_title, the resize + hstack of generate_comparison), on the
+ * device, reading the fused tail's padded outputs (mx_det_select) where they lie. The text is the
+ * project's own 5x7 bitmap font (csrc/mx_font5x7.h), not cv2's Hershey strokes, and the frames are not
+ * anti-aliased, so the pixels are this project's definition, stated here exactly.
+ * ------------------------------------------------------------------------------------------- */
+/* One descriptor per image, in a host array: */
+typedef struct mx_draw_desc {
+  const uint8_t* src;    /* device, u8 [H][W][3] */
+  uint8_t* dst;          /* device, u8 [bar + H][W][3]; may not overlap src */
+  const float* boxes;    /* device, f32 [D][4] xyxy; may be NULL when D == 0 */
+  const int64_t* labels; /* device, int64 [D]; may be NULL when D == 0 */
+  const float* scores;   /* device, f32 [D], or NULL: ground-truth mode (no threshold, no score text) */
+  const int32_t* count;  /* device, one int32: the rows 0..count-1 are candidates (count > D counts as D) */
+  int32_t H, W;          /* 1..32768 each */
+  int32_t D;             /* 0..2^20 */
+  int32_t bar;           /* title-bar height, 0..1024; 0: none */
+  int32_t title_len;     /* 0..64 */
+  char title[64];        /* title bytes (no terminator needed) */
+} mx_draw_desc;
+/* One launch per chunk of 16 images, one workgroup per output tile (mx_draw_batch_tile) of one image;
+ * descriptors, names and colours travel as the kernel argument: no workspace, no upload, no host
+ * synchronisation, capturable in a graph. The result does not depend on the launch geometry.
+ *   names_host: nnames <= 32 C strings of <= 15 bytes; entry k names label k + 1 (label 0 is the
+ *     detector's background); an empty string, or a label outside 1..nnames, renders as "cls<label>"
+ *     with the label in decimal ('-' for a negative one).
+ *   colors_host: u8 [ncolors][3], ncolors <= 32; entry k colours label k + 1, the three bytes applied
+ *     positionally to the image's channels 0, 1, 2 (the reference hands its RGB-looking triples to cv2
+ *     on BGR images; a drop-in does the same). Any other label takes (200, 200, 200).
+ *   label_scale, title_scale: integer font scales, 1..8. s = label_scale: th = 7*s and, for a text of
+ *     L bytes, tw = 6*s*L.
+ * Row i of an image is drawn when i < count and (scores == NULL or scores[i] >= conf_thr, false on NaN)
+ * and its four coordinates are finite with |c| < 2^20; any other row draws nothing and is not counted.
+ * (x1, y1, x2, y2) = the coordinates truncated toward zero. All ranges are inclusive, in image
+ * coordinates, clipped to the image:
+ *   frame: x1-1 <= x <= x2+1 and y1-1 <= y <= y2+1, less x1+1 <= x <= x2-1 and y1+1 <= y <= y2-1
+ *          (thickness 2), in the class colour;
+ *   plate: x1 <= x <= x1+tw+4 and y1-th-6 <= y <= y1, in the class colour;
+ *   text:  white (255, 255, 255): font pixel (col, row) of character k covers the s x s block whose
+ *          top-left is (x1 + 2 + 6*s*k + s*col, y1 - 3 - th + s*row). The text is the name, then in
+ *          score mode one space and the score as mx_draw_format_score writes it.
+ * Painter's order: within a row frame, plate, text; row i paints over every row j < i; a pixel no
+ * primitive touches keeps the source value. Title bar: output rows 0..bar-1 are (40, 40, 40) with the
+ * title in white at title_scale (tw, th from title_scale and title_len): glyph block top-left at
+ * x = floor((W - tw) / 2), y = floor((bar + th) / 2) - th, clipped to the bar; the image occupies rows
+ * bar..bar+H-1. drawn [n] int32 on the device: the number of rows drawn per image, or -1 when its
+ * count < 0 (then nothing is drawn). Every byte of every output is written; n == 0 and D == 0 are
+ * allowed. Every descriptor is checked before the first launch. */
+int mx_draw_batch_u8(const mx_draw_desc* descs_host, int64_t n, const char* const* names_host, int32_t nnames,
+                     const uint8_t* colors_host, int32_t ncolors, float conf_thr, int32_t label_scale,
+                     int32_t title_scale, int32_t* drawn, mx_stream_t stream);
+/* out[0], out[1] = rows, columns of the output tile one workgroup of mx_draw_batch_u8 owns; out[2] = the
+ * capacity of its row list (an image with more candidate rows is binned in chunks of that many). */
+int mx_draw_batch_tile(int32_t out[3]);
+/* The glyph table: out [95][7] u8, ASCII 32..126, 7 row bytes each (top row first), bit 4 = the leftmost
+ * of 5 columns. Host only. */
+int mx_draw_font(uint8_t* out);
+/* The score text of the overlay (host; the same function runs in the kernel): out = 4 bytes "d.dd" and
+ * a terminating 0. n = rint((double)s * 100) (the product is exact; rint rounds half to even, so the
+ * digits are those of printf("%.2f") of the exact f32 value), clamped to 0..999: s >= 9.995 prints
+ * "9.99"; a negative s, -0 or NaN prints "0.00". */
+int mx_draw_format_score(float s, char out[5]);
+/* One panel of mx_panels_compose_u8: */
+typedef struct mx_panel_desc {
+  const uint8_t* src; /* device, u8 [h][w][3] */
+  int32_t h, w;       /* 1..32768 each */
+  int32_t dw;         /* the panel's width on the canvas, 1..32768 */
+} mx_panel_desc;
+/* One launch: canvas u8 [target_h][sum(dw_p) + 3*(P-1)][3], 1 <= P <= 8, 1 <= target_h <= 32768. Panel p
+ * is resized to (dw_p, target_h) as cv2.resize's INTER_LINEAR does for u8 -- source index and the two
+ * 11-bit fixed-point taps per axis from the pixel-centre mapping (d + 0.5) * (src / dst) - 0.5 rounded
+ * to f32, clamped at the borders; horizontal pass, then the vertical combine
+ * (((S0 >> 4) * b0) >> 16) + (((S1 >> 4) * b1) >> 16) + 2 >> 2 -- the taps of the corruption kernels'
+ * low-res up-scale; a down-scale is plain bilinear with the same taps (no area averaging). Panels are
+ * laid left to right, separated by 3 columns of (200, 200, 200). The canvas may not overlap a panel. */
+int mx_panels_compose_u8(const mx_panel_desc* panels_host, int32_t P, int32_t target_h, uint8_t* canvas,
+                         mx_stream_t stream);
 /* Degradation statistics of a whole batch in one launch (csrc/mx_gate.hip), and a verdict per image from a
  * rule list over them: the blind gate in front of the restoration U-Net. The launch scheme of
  * mx_corrupt_batch_u8 (one workgroup per tile of one image, descriptors and rules as the kernel argument in

@@ -53,6 +53,19 @@ class WeatherDesc(ctypes.Structure):
                 ("fade", ctypes.c_int32), ("beta", ctypes.c_int32)]
 
 
+class DrawDesc(ctypes.Structure):
+    """mx_draw_desc (include/mx_det.h): one image of an mx_draw_batch_u8 call."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("boxes", ctypes.c_void_p),
+                ("labels", ctypes.c_void_p), ("scores", ctypes.c_void_p), ("count", ctypes.c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("D", ctypes.c_int32), ("bar", ctypes.c_int32),
+                ("title_len", ctypes.c_int32), ("title", ctypes.c_char * 64)]
+
+
+class PanelDesc(ctypes.Structure):
+    """mx_panel_desc (include/mx_det.h): one panel of an mx_panels_compose_u8 call."""
+    _fields_ = [("src", ctypes.c_void_p), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("dw", ctypes.c_int32)]
+
+
 class GateDesc(ctypes.Structure):
     """mx_gate_desc (include/mx_det.h): one image of an mx_degradation_stats_u8 call."""
     _fields_ = [("src", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("bgr", ctypes.c_int32)]
@@ -128,6 +141,12 @@ _SIGS = {
     "mx_corrupt_batch_tile": (c_int, [c_vp]),
     "mx_weather_batch_u8": (c_int, [c_vp, c_i64, c_vp, c_vp]),
     "mx_weather_batch_tile": (c_int, [c_vp]),
+    "mx_draw_batch_u8": (c_int, [c_vp, c_i64, c_vp, ctypes.c_int32, c_vp, ctypes.c_int32, c_f, ctypes.c_int32,
+                                 ctypes.c_int32, c_vp, c_vp]),
+    "mx_draw_batch_tile": (c_int, [c_vp]),
+    "mx_draw_font": (c_int, [c_vp]),
+    "mx_draw_format_score": (c_int, [c_f, c_vp]),
+    "mx_panels_compose_u8": (c_int, [c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
     "mx_degradation_stats_u8": (c_int, [c_vp, c_i64, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp]),
     "mx_degradation_stats_tile": (c_int, [c_vp]),
     "mx_restore_finish_gated": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),

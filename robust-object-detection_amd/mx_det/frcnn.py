@@ -886,6 +886,8 @@ class RoIHeads(nn.Module):
                                                             self.score_thresh, self.nms_thresh,
                                                             self.detections_per_img, ratios=ratios, weights=ROI_WEIGHTS,
                                                             max_seg=max(post, 1000))
+        if self.__dict__.get("_mx_padded"):  # FasterRCNN.detect_padded: the padded outputs, no host sync
+            return ob, osc, ol, counts
         counts = counts.tolist()  # the tail's one host sync
         if any(c < 0 for c in counts):
             raise RuntimeError("detection NMS: a class segment exceeded max_seg (num_keep < 0)")
@@ -1275,6 +1277,43 @@ class FasterRCNN(nn.Module):
         ev.record()
         return host, ev
 
+    def detect_padded(self, images):
+        """The eval forward with the fused detection tail's padded device outputs as they are, without the
+        tail's host sync: (boxes [N, D, 4] f32 xyxy in the original image's pixels, scores [N, D], labels
+        [N, D] int64, counts [N] int32), D = detections_per_img, rows past an image's count zero -- what
+        mx_det.draw.Overlay.batch and the device COCOeval read in place. Works under model.tta and an
+        enabled BNAdapter as the plain forward does. A count of -1 (a class segment over the NMS's
+        max_seg) cannot raise here without waiting for the GPU: a flag is copied to pinned memory
+        asynchronously and check_padded() -- called by the next detect_padded, or by the caller once it
+        has synchronised anyway -- raises the RuntimeError the plain forward raises."""
+        if self.training:
+            raise RuntimeError("detect_padded is an eval-mode call")
+        if not hasattr(self.be, "detections_postprocess"):
+            raise NotImplementedError(f"backend {getattr(self.be, 'name', type(self.be).__name__)!r} has no fused "
+                                      "detection tail (detections_postprocess is a chain of HIP kernels)")
+        self.check_padded()
+        self.roi_heads.__dict__["_mx_padded"] = True
+        try:
+            ob, osc, ol, counts = self(images)
+        finally:
+            del self.roi_heads.__dict__["_mx_padded"]
+        host = self.__dict__.get("_padded_host")
+        if host is None:
+            host = self.__dict__["_padded_host"] = torch.empty((), dtype=torch.bool, pin_memory=True)
+        host.copy_((counts < 0).any(), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.__dict__["_padded_pending"] = ev
+        return ob, osc, ol, counts
+
+    def check_padded(self):
+        """Raise when the last detect_padded produced a count of -1 (waits for that forward only)."""
+        ev = self.__dict__.pop("_padded_pending", None)
+        if ev is not None:
+            ev.synchronize()
+            if bool(self.__dict__["_padded_host"]):
+                raise RuntimeError("detection NMS: a class segment exceeded max_seg (num_keep < 0)")
+
     def forward(self, images, targets=None):
         be = self.be
         if hasattr(be, "prepare"):
@@ -1335,7 +1374,7 @@ class FasterRCNN(nn.Module):
         defer = os.environ.get("MX_RPN_DEFER_LOSSES", "0") != "0"
         stage = self._stage(il, features, head, targets, be) if not defer else None
         # eval: the whole detection tail on the device (always under test-time augmentation)
-        fused = tta is not None or self.roi_heads.fused_active(be)
+        fused = tta is not None or self.roi_heads.fused_active(be) or bool(self.roi_heads.__dict__.get("_mx_padded"))
         try:
             if stage is not None:  # HIP-graph replay of the proposal stage (no autograd inside)
                 objectness, pred_deltas = head[0], head[1]
