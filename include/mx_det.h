@@ -478,6 +478,52 @@ int mx_degradation_stats_u8(const mx_gate_desc* descs_host, int64_t n, const mx_
                             int32_t default_verdict, int64_t* stats, int32_t* verdict, mx_stream_t stream);
 /* out[0], out[1] = rows, columns of the tile of interior pixels one workgroup of mx_degradation_stats_u8 owns. */
 int mx_degradation_stats_tile(int32_t out[2]);
+/* Blind non-local means over a whole batch in one launch (csrc/mx_denoise.hip): the pixel branch for the
+ * images the gate's noise rule recognises, with the strength taken per image from the gate's own sums on the
+ * device. The launch scheme of mx_degradation_stats_u8 (one workgroup per output tile of one image, descriptors
+ * as the kernel argument in chunks of 16 images: no workspace, no upload, no host synchronisation, no
+ * allocation, capturable in a graph); images of one call may differ in size. Every value is an unsigned integer.
+ *   Constants: patch radius 2 (5 x 5), search radius 5 (11 x 11 = 121 candidates, the centre included);
+ *   coordinates outside the image clamp to the nearest pixel; luma Y = (77 R + 150 G + 29 B + 128) >> 8 (bgr
+ *   as in mx_gate_desc); LUT[i] = round(4096 * exp(-i / 16)) for i = 0..127 as committed literals
+ *   (mx_denoise_nlm_lut), weight 0 from index 128 up.
+ *   Per image: s8 = the luma noise sigma in 1 / 256 grey levels.
+ *     sigma_q8 in 1..65535: s8 = sigma_q8 and the image is denoised.
+ *     sigma_q8 == 0 (blind): from stats[b] = { N, IMM, ... } as mx_degradation_stats_u8 wrote them,
+ *       a = (IMM << 8) / N, s8 = (a * 13689) >> 16 (13689 / 65536 = 1.2533 / 6, Immerkaer's scale); the image
+ *       is denoised only when rule_a * IMM > rule_b * N (the gate's noise rule: 10, 383).
+ *     With a verdict array, an image is denoised only if verdict[b] == 0 as well (the U-Net's images are left
+ *     alone).
+ *     T0 = (50 * s8 * s8) >> 16      (the expected patch distance of pure noise, 25 * 2 sigma^2)
+ *     D  = max((25 * k16 * k16 * s8 * s8) >> 24, 1)      (h = k16 / 16 sigma; k16 = 6: h = 0.375 sigma)
+ *     Q  = (1 << 24) / D
+ *     An image that is not denoised has dst = the bytes of src. applied[b] = 1 for a denoised image, else 0.
+ *   Per pixel p and candidate q = p + (dy, dx), |dy|, |dx| <= 5:
+ *     d   = sum over |u|, |v| <= 2 of (Y(p + uv) - Y(q + uv))^2        (< 2^21)
+ *     t   = max(d - T0, 0)
+ *     idx = min((t * Q) >> 20, 128)                                     (t * Q < 2^45, in 64 bits)
+ *     w   = LUT[idx], Wsum = sum w  (>= 4096: the centre has t = 0; < 2^19)
+ *     out_c(p) = (sum w * X_c(q) + (Wsum >> 1)) / Wsum per channel      (sum w * X < 2^27)
+ *   X is read from src: results never feed back. With valid stats a <= 2040 * 256 and s8 < 2^17, so every
+ *   product above stays below 2^63. */
+typedef struct mx_nlm_desc {
+  const uint8_t* src; /* device, u8 [H][W][3] */
+  uint8_t* dst;       /* device, u8 [H][W][3]; may overlap no src of the call */
+  int32_t H, W;       /* >= 1 each (>= 3 for a blind image), H * W <= 2^24 */
+  int32_t bgr;        /* 0: channel 0 is R; else channel 0 is B */
+  int32_t sigma_q8;   /* 0: blind, from stats; 1..65535: the luma sigma in 1 / 256 grey levels */
+} mx_nlm_desc;
+/* stats: device int64 [n][8], may be NULL when every sigma_q8 > 0; verdict: device int32 [n] or NULL; applied:
+ * device int32 [n] or NULL. Refused before any launch (MX_EINVAL, with a message): null pointers, H or W < 1,
+ * H * W > 2^24, sigma_q8 outside 0..65535, a blind image without stats or with H or W < 3, k16 outside 1..64,
+ * rule coefficients outside 0..65535, a dst that overlaps a src (a tile reads pixels another tile writes).
+ * n == 0 launches nothing. */
+int mx_denoise_nlm_u8(const mx_nlm_desc* descs_host, int64_t n, const int64_t* stats, const int32_t* verdict,
+                      int32_t rule_a, int32_t rule_b, int32_t k16, int32_t* applied, mx_stream_t stream);
+/* out[0], out[1] = rows, columns of the output tile one workgroup of mx_denoise_nlm_u8 owns. */
+int mx_denoise_nlm_tile(int32_t out[2]);
+/* The 128 weights of mx_denoise_nlm_u8's table. Host only. */
+int mx_denoise_nlm_lut(int32_t out[128]);
 /* GeneralizedRCNNTransform (normalize, zero-pad to /32) fused with ToDtype(scale=True):
  * u8 HWC [B,H,W,3] -> NHWC [B, Hp, Wp, Cp] dtype, (x/255 - mean)/std, zero padding; Cp >= 3 (extra
  * channels zero, for the conv stem's 8-channel gather). */

@@ -71,6 +71,12 @@ class GateDesc(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("bgr", ctypes.c_int32)]
 
 
+class NlmDesc(ctypes.Structure):
+    """mx_nlm_desc (include/mx_det.h): one image of an mx_denoise_nlm_u8 call."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("bgr", ctypes.c_int32), ("sigma_q8", ctypes.c_int32)]
+
+
 class GateRule(ctypes.Structure):
     """mx_gate_rule (include/mx_det.h): fires when a * stats[i] > b * stats[j]."""
     _fields_ = [("i", ctypes.c_int32), ("j", ctypes.c_int32), ("a", ctypes.c_int32), ("b", ctypes.c_int32),
@@ -150,6 +156,9 @@ _SIGS = {
     "mx_degradation_stats_u8": (c_int, [c_vp, c_i64, c_vp, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp, c_vp]),
     "mx_degradation_stats_tile": (c_int, [c_vp]),
     "mx_restore_finish_gated": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "mx_denoise_nlm_u8": (c_int, [c_vp, c_i64, c_vp, c_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_vp, c_vp]),
+    "mx_denoise_nlm_tile": (c_int, [c_vp]),
+    "mx_denoise_nlm_lut": (c_int, [c_vp]),
     "mx_normalize_pad": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp]),
     "mx_resize_normalize_pad": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_int,
                                         c_vp, c_vp]),

@@ -213,16 +213,26 @@ class GatedRestorer:
         on the device; no host synchronisation (the counts stay on the device until they are read).
       mode "skip": the verdicts are read once, the U-Net runs on the flagged images only, the others are
         copied. The same bytes as "select".
-    restored / passed count the images of both kinds since the last take_counts()."""
+    denoiser (a denoise.NLMDenoiser, or None): the pixel branch for noise. An image the U-Net leaves alone
+    (verdict 0) and the denoiser's rule recognises as noisy is denoised, blind, from the gate's own sums
+    (mx_denoise_nlm_u8): in select mode the stats and verdicts go to it on the device after the U-Net's
+    selection and the host still never waits; skip mode makes the same decisions from its one read-back.
+    restored / denoised / passed count the images of each kind since the last take_counts(); without a
+    denoiser nothing changes and take_counts() has its two keys."""
 
-    def __init__(self, unet, rules=DEFAULT_RULES, default=DEFAULT_VERDICT, mode="select", bgr=False):
+    def __init__(self, unet, rules=DEFAULT_RULES, default=DEFAULT_VERDICT, mode="select", bgr=False, denoiser=None):
         if mode not in ("select", "skip"):
             raise ValueError(f"GatedRestorer mode {mode!r}: select or skip")
         self.unet, self.mode, self.bgr = unet, mode, bool(bgr)
         self.rules, self.default = check_rules(rules, default), int(default)
+        if denoiser is not None and bool(denoiser.bgr) != self.bgr:
+            raise ValueError("GatedRestorer: the denoiser's bgr differs from the gate's")
+        self.denoiser = denoiser
         self._seen = 0
         self._restored = 0      # host part (skip mode)
         self._restored_dev = None  # device part (select mode): an int64 scalar, summed without a sync
+        self._denoised = 0
+        self._denoised_dev = None
 
     # -- counts
     @property
@@ -231,13 +241,22 @@ class GatedRestorer:
         return self._restored + dev
 
     @property
+    def denoised(self):
+        dev = int(self._denoised_dev.item()) if self._denoised_dev is not None else 0
+        return self._denoised + dev
+
+    @property
     def passed(self):
-        return self._seen - self.restored
+        return self._seen - self.restored - (self.denoised if self.denoiser is not None else 0)
 
     def take_counts(self):
-        """{"restored", "passed"} since the last call, and start again from zero."""
+        """{"restored", "passed"} since the last call (with a denoiser: and "denoised", which passed then
+        excludes), and start again from zero."""
         out = {"restored": self.restored, "passed": self.passed}
+        if self.denoiser is not None:
+            out["denoised"] = self.denoised
         self._seen, self._restored, self._restored_dev = 0, 0, None
+        self._denoised, self._denoised_dev = 0, None
         return out
 
     # -- verdicts
@@ -250,11 +269,28 @@ class GatedRestorer:
         """The verdicts as a list of ints (one read-back)."""
         return [int(v) for v in self.verdicts(images)[1].tolist()]
 
-    def count(self, verdicts):
+    def _denoise_decisions(self, rows, verdicts):
+        """The device's apply decision per image, restated on the host (denoise.params)."""
+        from . import denoise
+        d = self.denoiser
+        return [int(denoise.params(row, d.k16, d.rule, verdict=v)[0]) for row, v in zip(rows, verdicts)]
+
+    def decide_both_u8(self, images):
+        """(stats, verdicts, denoise) with one read-back: the device stats, the verdicts as ints and, per image,
+        1 when the denoiser would take it (all 0 without a denoiser)."""
+        import torch
+        stats, verdict = self.verdicts(images)
+        rows = torch.cat([stats, verdict[:, None].to(torch.int64)], 1).tolist()
+        v = [int(r[8]) for r in rows]
+        dn = self._denoise_decisions([r[:8] for r in rows], v) if self.denoiser is not None else [0] * len(v)
+        return stats, v, dn
+
+    def count(self, verdicts, denoised=()):
         """Count images decided outside restore_u8 (scripts that copy passed files themselves)."""
         verdicts = [int(v) for v in verdicts]
         self._seen += len(verdicts)
         self._restored += sum(verdicts)
+        self._denoised += sum(int(v) for v in denoised)
 
     # -- restore
     def restore_u8(self, img_u8):
@@ -264,14 +300,22 @@ class GatedRestorer:
         xs = img_u8 if batched else list(img_u8)
         if len(xs) == 0:
             return img_u8 if batched else []
-        _, verdict = self.verdicts(xs)
+        if self.denoiser is not None and self.mode == "skip":
+            return self._restore_skip_denoise(xs, batched)
+        stats, verdict = self.verdicts(xs)
         if self.mode == "select":
             self._seen += len(xs)
             s = verdict.sum(dtype=torch.int64)
             self._restored_dev = s if self._restored_dev is None else self._restored_dev + s
             if batched:
-                return self.unet.restore_u8(xs, verdict=verdict)
-            return [self.unet.restore_u8(im[None], verdict=verdict[b:b + 1])[0] for b, im in enumerate(xs)]
+                out = self.unet.restore_u8(xs, verdict=verdict)
+            else:
+                out = [self.unet.restore_u8(im[None], verdict=verdict[b:b + 1])[0] for b, im in enumerate(xs)]
+            if self.denoiser is not None:  # the U-Net's images are copied, the noisy ones denoised: one launch
+                out, applied = self.denoiser.denoise_u8(out, stats=stats, verdict=verdict)
+                s = applied.sum(dtype=torch.int64)
+                self._denoised_dev = s if self._denoised_dev is None else self._denoised_dev + s
+            return out
         v = [int(k) for k in verdict.tolist()]
         self.count(v)
         if batched:
@@ -283,8 +327,23 @@ class GatedRestorer:
             return out
         return [self.unet.restore_u8(im[None])[0] if k else im.clone() for im, k in zip(xs, v)]
 
+    def _restore_skip_denoise(self, xs, batched):
+        """Skip mode with a denoiser: the U-Net on the flagged images, the denoiser (blind, from the device
+        stats of exactly those images) on the noisy ones, copies of the rest."""
+        import torch
+        stats, v, dn = self.decide_both_u8(xs)
+        self.count(v, dn)
+        outs = [self.unet.restore_u8(im[None])[0] if k else (None if d else im.clone()) for im, k, d in zip(xs, v, dn)]
+        idx = [b for b, d in enumerate(dn) if d]
+        if idx:
+            sel = torch.tensor(idx, device=stats.device)
+            got, _ = self.denoiser.denoise_u8([xs[b] for b in idx], stats=stats.index_select(0, sel).contiguous())
+            for b, g in zip(idx, got):
+                outs[b] = g
+        return torch.stack(outs) if batched else outs
 
-def from_env(unet, mode="select", value=None):
+
+def from_env(unet, mode="select", value=None, denoiser=None):
     """The GatedRestorer MX_RESTORE_GATE asks for, or None when the gate is off."""
     g = env_gate(value)
-    return None if g is None else GatedRestorer(unet, g[0], g[1], mode=mode)
+    return None if g is None else GatedRestorer(unet, g[0], g[1], mode=mode, denoiser=denoiser)

@@ -1025,6 +1025,58 @@ def degradation_stats_u8(images, rules=None, default=0, bgr=False, out=None):
     return stats, verdict
 
 
+def denoise_nlm_tile():
+    """(rows, columns) of the output tile one workgroup of mx_denoise_nlm_u8 owns."""
+    rc = (ctypes.c_int32 * 2)()
+    call("mx_denoise_nlm_tile", rc)
+    return int(rc[0]), int(rc[1])
+
+
+def denoise_nlm_lut():
+    """The 128 weights of mx_denoise_nlm_u8's table, as a list of ints."""
+    out = (ctypes.c_int32 * 128)()
+    call("mx_denoise_nlm_lut", out)
+    return [int(v) for v in out]
+
+
+def denoise_nlm_u8(images, stats=None, verdict=None, sigma=None, k16=6, rule=(10, 383), bgr=False, out=None):
+    """Non-local means (5 x 5 patches of luma, an 11 x 11 search window, integer arithmetic; include/mx_det.h
+    defines it) on every image of a batch in one device launch (mx_denoise_nlm_u8; chunks of 16 images), with
+    no host synchronisation: images is uint8 [B,H,W,3] or a list of uint8 [H,W,3] tensors of any sizes.
+    sigma: the luma noise sigma in grey levels, a float or one per image (rounded to 1/256, 1/256..255.996);
+    such an image is denoised. sigma None (or None for an image): blind -- the image's strength comes from
+    stats[b] (int64 [B,8] on the device, as degradation_stats_u8 returns them; H, W >= 3), and it is denoised
+    only when rule[0] * IMM > rule[1] * N, the gate's noise rule. verdict (int32 [B] on the device): an image
+    with verdict[b] != 0 is left alone. k16 in 1..64: the filter strength h = k16 / 16 sigma. An image that is
+    not denoised is copied. out: a tensor / list like images to write into; it may overlap no image. Returns
+    (out, applied): a tensor for a tensor, a list for a list; applied int32 [B] on the device, 1 = denoised."""
+    batched, x, xs, out, outs = _batch_io(images, out, "denoise_nlm_u8")
+    B = len(xs)
+    device = xs[0].device if B else (images.device if batched else torch.device("cuda", torch.cuda.current_device()))
+    sig = list(sigma) if isinstance(sigma, (list, tuple)) else [sigma] * B
+    _check(len(sig) == B, "denoise_nlm_u8: one sigma per image")
+    q8 = [0 if s is None else int(round(float(s) * 256.0)) for s in sig]
+    _check(all(s is None or 1 <= q <= 65535 for s, q in zip(sig, q8)), "denoise_nlm_u8: sigma must round to 1/256..65535/256")
+    a, b = (int(v) for v in rule)
+    if stats is not None:
+        _dev(stats)
+        _check(stats.dtype == torch.int64 and tuple(stats.shape) == (B, 8) and stats.is_contiguous() and stats.device == device,
+               "denoise_nlm_u8: stats must be a contiguous int64 [B,8] tensor on the images' device")
+    if verdict is not None:
+        _dev(verdict)
+        _check(verdict.dtype == torch.int32 and tuple(verdict.shape) == (B,) and verdict.is_contiguous()
+               and verdict.device == device, "denoise_nlm_u8: verdict must be a contiguous int32 [B] tensor on the images' device")
+    applied = torch.empty((B,), dtype=torch.int32, device=device)
+    descs = (_lib.NlmDesc * max(B, 1))()
+    for d, im, o, q in zip(descs, xs, outs, q8):
+        d.src, d.dst, d.H, d.W = im.data_ptr(), o.data_ptr(), int(im.shape[0]), int(im.shape[1])
+        d.bgr, d.sigma_q8 = int(bool(bgr)), q
+    # the library checks sizes, sigma, k16, the rule and overlap before it launches anything
+    call("mx_denoise_nlm_u8", descs, B, _p(stats) if stats is not None and B else None,
+         _p(verdict) if verdict is not None and B else None, a, b, int(k16), _p(applied) if B else None, _stream())
+    return (out if batched else outs), applied
+
+
 IMAGE_MEAN = (0.485, 0.456, 0.406)
 IMAGE_STD = (0.229, 0.224, 0.225)
 

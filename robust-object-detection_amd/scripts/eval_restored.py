@@ -16,6 +16,11 @@ of every variant, Test_Clean included, gets its degradation statistics on the de
 passed through by their verdict (mx_det.gate.GatedRestorer, mode select: no host synchronisation). Results
 go to experiments/eval_restored_results_gated.json (reference schema), the per-variant restored / passed
 counts to experiments/restore_gate_counts.json.
+MX_RESTORE_DENOISE (nlm or nlm:<k16>; unset or 0: off; needs the gate and MX_RESTORE_ON_DEVICE=1, otherwise
+ValueError before any model loads): the images the gate's noise rule recognises, which the U-Net leaves alone,
+go through the blind non-local-means denoiser (mx_det.denoise; one more device launch per batch, still no host
+synchronisation). Results go to experiments/eval_restored_results_gated_nlm.json (reference schema), and the
+counts file gains the denoised counts. The denoiser's effect on mAP is unmeasured.
 MX_EXTRA_VARIANTS=jpeg evaluates the restored Test_JPEG set too, MX_SEVERITIES the restored
 Test_<Kind>_s<L> sets (eval_all.all_variants()).
 MX_BN_ADAPT=<mode>[:<prior>] adds a <name>_BNAdapt entry per checkpoint: the same run with test-time BatchNorm
@@ -27,7 +32,7 @@ from pathlib import Path
 import torch
 
 from mx_det import adapt as bn_adapt
-from mx_det import gate
+from mx_det import denoise, gate
 from mx_det.unet import RestorationUNet
 from scripts import eval_all
 
@@ -47,9 +52,9 @@ def load_unet(dev, ckpt=None):
     return unet.to(dev).eval()
 
 
-def results_name(on_device, gated=False):
+def results_name(on_device, gated=False, denoised=False):
     if on_device and gated:
-        return "eval_restored_results_gated.json"
+        return "eval_restored_results_gated_nlm.json" if denoised else "eval_restored_results_gated.json"
     return "eval_restored_results_fused.json" if on_device else "eval_restored_results.json"
 
 
@@ -58,12 +63,15 @@ def main():
     on_device = os.environ.get("MX_RESTORE_ON_DEVICE", "0") != "0"
     adapt = bn_adapt.parse_env(os.environ.get("MX_BN_ADAPT", ""))
     rules = gate.env_gate() if on_device else None  # a bad rules file raises here, before any model loads
+    denoiser = denoise.env_denoise()  # and so does a bad MX_RESTORE_DENOISE
+    if denoiser is not None and rules is None:
+        raise ValueError("MX_RESTORE_DENOISE needs the gate (MX_RESTORE_GATE) and MX_RESTORE_ON_DEVICE=1")
     restorer = load_unet(dev) if on_device else None
     root = CORRUPTED_ROOT if on_device else RESTORED_ROOT
     results, counts = {}, {}
     kw = {}
     if rules is not None:
-        restorer = gate.GatedRestorer(restorer, rules[0], rules[1], mode="select")
+        restorer = gate.GatedRestorer(restorer, rules[0], rules[1], mode="select", denoiser=denoiser)
         kw = dict(restore_clean=True)
     for name, ck in CKPTS.items():
         if rules is not None:
@@ -80,7 +88,7 @@ def main():
                 results[aname] = r
     if rank == 0:
         OUT_DIR.mkdir(parents=True, exist_ok=True)
-        eval_all.save_json(results, OUT_DIR / results_name(on_device, rules is not None))
+        eval_all.save_json(results, OUT_DIR / results_name(on_device, rules is not None, denoiser is not None))
         if rules is not None:
             eval_all.save_json(counts, OUT_DIR / "restore_gate_counts.json")
     return results

@@ -12,6 +12,9 @@ MX_RESTORE_GATE (unset or 0: off, auto, or a rules JSON; mx_det.gate): the blind
 image it passes is copied as a file (shutil.copy2: no JPEG round trip), one it flags is restored and encoded
 as above; Test_Clean goes through the gate like the others. Output goes to data/testsets/coco6_gated, the
 per-variant restored / passed counts are printed.
+MX_RESTORE_DENOISE (nlm or nlm:<k16>; needs the gate, otherwise ValueError before any model loads): an image
+the gate's noise rule recognises goes through the blind non-local-means denoiser (mx_det.denoise) and is
+encoded and written; passed files are copied as before. Output goes to data/testsets/coco6_gated_nlm.
 """
 import os
 import shutil
@@ -22,13 +25,14 @@ import torch
 from PIL import Image
 
 from scripts import eval_restored
-from mx_det import gate, jpeg
+from mx_det import denoise, gate, jpeg
 from mx_det.augment import env_extra_variants, severity_variants
 from mx_det.engine import init_device
 
 COCO_TESTSET_ROOT = Path("data/testsets/coco6")
 COCO_OUT_ROOT = Path("data/testsets/coco6_restored")
 COCO_GATED_ROOT = Path("data/testsets/coco6_gated")
+COCO_GATED_NLM_ROOT = Path("data/testsets/coco6_gated_nlm")
 VARIANTS_TO_RESTORE = ["Test_Noise", "Test_Blur", "Test_LowRes"]
 
 
@@ -69,12 +73,17 @@ def restore_variant(unet, variant, dev, src_root=None, dst_root=None):
     files = sorted(src_img.glob("*.jpg"))
     for i, p in enumerate(files):
         img = read_rgb(p, dev)[None]
-        verdict = 1
-        if gated:  # skip mode, with the file itself as the passed image's copy
+        verdict, noisy = 1, 0
+        if gated and unet.denoiser is not None:
+            stats, (verdict,), (noisy,) = unet.decide_both_u8(img)
+            unet.count([verdict], [noisy])
+        elif gated:  # skip mode, with the file itself as the passed image's copy
             verdict = unet.decide_u8(img)[0]
             unet.count([verdict])
         if verdict:
             write_rgb(dst_img / p.name, (unet.unet if gated else unet).restore_u8(img)[0])
+        elif noisy:
+            write_rgb(dst_img / p.name, unet.denoiser.denoise_u8(img, stats=stats)[0][0])
         else:
             shutil.copy2(p, dst_img / p.name)
         if (i + 1) % 100 == 0 or i + 1 == len(files):
@@ -84,11 +93,15 @@ def restore_variant(unet, variant, dev, src_root=None, dst_root=None):
 def main():
     dev, _, _ = init_device()
     rules = gate.env_gate()  # a bad rules file raises here
+    denoiser = denoise.env_denoise()  # and a bad MX_RESTORE_DENOISE here
+    if denoiser is not None and rules is None:
+        raise ValueError("MX_RESTORE_DENOISE needs the gate (MX_RESTORE_GATE)")
     unet = eval_restored.load_unet(dev)
     if rules is not None:
-        gated = gate.GatedRestorer(unet, rules[0], rules[1], mode="skip")
+        gated = gate.GatedRestorer(unet, rules[0], rules[1], mode="skip", denoiser=denoiser)
+        dst_root = COCO_GATED_ROOT if denoiser is None else COCO_GATED_NLM_ROOT
         for v in ["Test_Clean"] + variants_to_restore():
-            restore_variant(gated, v, dev, dst_root=COCO_GATED_ROOT)
+            restore_variant(gated, v, dev, dst_root=dst_root)
             print(f"    gate {v}: {gated.take_counts()}", flush=True)
         return
     for v in variants_to_restore():
